@@ -14,6 +14,12 @@ gathered to rank 0 over RCCL at the end of each step, as in configs[3].  The col
 (barrier, max-over-ranks time, the trajectory gather) are libtcmp.so's own RCCL
 communicator (tcmp_dist_*, tcmp_gather_paths): no PyTorch in this process.
 
+A plain run sets up, warms up, times the steps and prints the line.  --full adds everything else
+the bench measures, after the timed steps: the device's measured peaks, the per-kernel timing
+pass and the rooflines it feeds, the one-query-at-a-time pass, the CPU baseline, the
+default-batch line and the C4 / C5 sub-lines.  --dump-outputs DIR writes what the last timed step
+returned (dump_outputs below).
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -330,6 +336,43 @@ def quality(res):
             "status_counts": st}
 
 
+OUTCOME_FIELDS = ("status", "goal_found", "n_nodes", "n_samples", "goal_node", "n_waypoints",
+                  "n_traj", "goal_cost", "goal_depth")
+DUMP_MAX_BYTES = 60_000_000  # all files together, headers included, stay under 64 MB
+
+
+def dump_outputs(out_dir, step, rank=None, trees=False):
+    """--dump-outputs: what the last timed step's queries computed, as DIR/<name>.npy (float64).
+    step: (result, fetched arrays or None, engine) per query.  Per query `result` (the plan's
+    outcome, OUTCOME_FIELDS in order); `tree`, the tree its rounds grew (tcmp_plan_tree: a row per
+    node -- configuration, cost, parent index; never empty: the root), when `trees` says the
+    engines still hold their queries' trees; and, when the query found a path (one in five C3
+    queries does not), the fetched `waypoints`, `q`, `qd`, `qdd`, `psg`, `tau`.  A step of several
+    queries prefixes q<index>_, a run of several ranks rank<r>_.  The queries' scenes, goals and
+    seeds depend on the arguments alone, so two builds run with the same arguments write
+    comparable files.  The smaller arrays are written whole; one past its share of what is left of
+    DUMP_MAX_BYTES is cut to a fixed, seeded sample of its rows (C3's 1e6-node tree is)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    for j, (r, out, eng) in enumerate(step):
+        pre = "rank%d_" % rank if rank is not None else ""
+        pre += "q%02d_" % j if len(step) > 1 else ""
+        arrays[pre + "result"] = np.array([getattr(r, f) for f in OUTCOME_FIELDS], dtype=np.float64)
+        if trees:
+            cfg, cost, par, _ = eng.plan_tree(r.n_nodes)
+            arrays[pre + "tree"] = np.column_stack([cfg, cost, par]).astype(np.float64)
+        for k, a in (out or {}).items():
+            arrays[pre + k] = np.asarray(a, dtype=np.float64)
+    left = DUMP_MAX_BYTES
+    for i, (name, a) in enumerate(sorted(arrays.items(), key=lambda x: x[1].nbytes)):
+        share = left // (len(arrays) - i)
+        if a.nbytes > share:
+            keep = share // (a.nbytes // len(a))
+            a = a[np.sort(np.random.default_rng(0).choice(len(a), keep, replace=False))]
+        left -= a.nbytes
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -343,6 +386,15 @@ def parse_args(argv=None):
     ap.add_argument("--queries", type=int, default=None,
                     help="queries per step over all ranks (c4: 64; --queries 8 on one GPU is "
                          "one GPU's share of c4 at N = 8)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline value does not "
+                         "need: the device's peaks, the per-kernel timing pass and rooflines, "
+                         "config_single_query, cpu_baseline, config_alt and the config_c4 / "
+                         "config_c5 sub-lines (each still has its own --no-... switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float64): "
+                         "per query the plan's outcome, its tree (single-query workloads) and, "
+                         "if it found a path, the waypoints / trajectory arrays")
     ap.add_argument("--cpu-samples", type=int, default=40000)
     ap.add_argument("--cpu-workers", type=int, default=usable_cores(),
                     help="worker processes of the multi-core CPU baseline (default: every "
@@ -404,9 +456,9 @@ def main():
     # rooflines), condensed; one GPU only (at N > 1 run --workload c4 / c5 for the sharded form)
     default_c3 = (args.workload == "c3" and args.samples is None and args.batch is None and
                   args.obstacles is None and not args.shared_tree and not args.self_collisions)
-    if world == 1 and default_c3 and not args.no_sublines:
+    if args.full and world == 1 and default_c3 and not args.no_sublines:
         for wl, steps in (("c4", args.steps), ("c5", args.c5_steps)):
-            sub = parse_args(["--workload", wl, "--steps", str(max(1, steps)), "--warmup",
+            sub = parse_args(["--full", "--workload", wl, "--steps", str(max(1, steps)), "--warmup",
                               str(min(1, args.warmup)), "--no-cpu-baseline", "--no-alt",
                               "--no-single"])
             try:
@@ -445,10 +497,12 @@ def measure(args, world, rank, gpu, comm):
 
     eng = _lib.Engine(gpu)
     # the spec peaks re-measured on this device, reported beside the spec figures
-    try:
-        measured = eng.microbench()
-    except _lib.TcmpError as e:  # older library builds (A/B runs) lack the entry point
-        measured = {"error": str(e)}
+    measured = {}
+    if args.full:
+        try:
+            measured = eng.microbench()
+        except _lib.TcmpError as e:  # older library builds (A/B runs) lack the entry point
+            measured = {"error": str(e)}
     # query ids of this rank: c4 shards 64 queries round-robin (scene and goal fixed per query
     # id); the single-query workloads run the same scene (query id 0) on every rank with
     # rank-dependent sample seeds -- independent trees of identical expected work, so the
@@ -535,18 +589,21 @@ def measure(args, world, rank, gpu, comm):
                 if fleets:
                     # a fleet of (query, step) pairs on this thread's group of engines
                     pairs = jobs[idx]
-                    done = run_fleet(engines[k * fleet:(k + 1) * fleet],
-                                     [queries[j] for j, _ in pairs], W["samples"], W["batch"],
+                    grp = engines[k * fleet:(k + 1) * fleet]
+                    done = run_fleet(grp, [queries[j] for j, _ in pairs], W["samples"], W["batch"],
                                      [step_seed(s) + 7919 * j for j, s in pairs], mode, mass)
-                    got += [(idx * fleet + t, s) + d for t, ((_, s), d) in enumerate(zip(pairs, done))]  # noqa: E501
+                    got += [(idx * fleet + t, s) + d + (e,)
+                            for t, ((_, s), d, e) in enumerate(zip(pairs, done, grp))]
                     continue
                 j, s = jobs[idx]
                 obs, pack, goal = queries[j]
                 got.append((idx, s) + run_query(engines[k], obs, goal, W["samples"], W["batch"],
                                                 step_seed(s) + 7919 * j, mode, mass, meshes=pack,
-                                                shared=comm if shared else None))
+                                                shared=comm if shared else None) + (engines[k],))
         return sorted(sum(pool.map(lane, range(n_streams)) if pool else [lane(0)], []),
                       key=lambda x: x[0])
+
+    last_step = []  # (result, fetched arrays or None, engine) of the newest step's queries
 
     def step_group(ss):
         pairs = [(j, s) for s in ss for j in range(len(queries))]
@@ -564,6 +621,7 @@ def measure(args, world, rank, gpu, comm):
         for s in ss:
             part = [d for d in done if d[1] == s]
             outs = [d[3] for d in part]
+            last_step[:] = [d[2:5] for d in part]
             res += [d[2].as_dict() for d in part]
             if comm is not None and not shared:
                 # RCCL gather of the solved trajectories (q, qd, qdd, dt) to rank 0 (configs[3]),
@@ -596,6 +654,10 @@ def measure(args, world, rank, gpu, comm):
     barrier()
     dt = time.perf_counter() - t0
     log("timed steps done: %.3f s" % dt)
+    if args.dump_outputs:
+        # a one-query step is the last job its engine ran, so the engine still holds its tree
+        dump_outputs(args.dump_outputs, last_step, rank if world > 1 else None,
+                     trees=len(queries) == 1)
     # samples the devices actually drew (tcmp_plan_result.n_samples), summed over all ranks
     total_samples = float(sum(x["n_samples"] for x in results))
     if comm is not None:
@@ -613,7 +675,7 @@ def measure(args, world, rank, gpu, comm):
     # one-query-at-a-time throughput (config_single_query), same build, same box.
     kres = results
     single = None
-    if fleets and not lead_timed:
+    if args.full and fleets and not lead_timed:
         # fused rounds: S fleets one at a time on one group of engines, timed on its first
         # engine (the fleet's kernel times are reported there; every plan counts the rounds);
         # a fleet = the first `fleet` (query, step) pairs' queries, fresh seeds
@@ -631,7 +693,7 @@ def measure(args, world, rank, gpu, comm):
         grp[0].synchronize()
         grp[0].set_timing(False)
         barrier()
-    if n_engines > 1 and (not fleets or (len(queries) == 1 and not args.no_single)):
+    if args.full and n_engines > 1 and (not fleets or (len(queries) == 1 and not args.no_single)):
         e0 = engines[0]
         e0.set_timing(True)
         obs, pack, goal = queries[0]
@@ -793,6 +855,12 @@ def measure(args, world, rank, gpu, comm):
         # rank 0's timed queries: rounds, goal rate, path cost / depth, statuses
         "quality": quality(results),
     }
+    if not (args.full or n_engines == 1 or lead_timed):
+        # queries in flight ran untimed per kernel and no timing pass followed (--full runs it)
+        for k in ("roofline", "roofline_other", "kernel_ms_per_step", "kernel_timing"):
+            del line[k]
+    if not args.full:
+        del line["measured_peaks"]
     if comm is not None:
         # proof of the collective world the run used: RCCL's own rank count, and rank 0's check
         # that every gather delivered every query id with the all-gathered row counts
@@ -812,13 +880,13 @@ def measure(args, world, rank, gpu, comm):
             line["gather_ok"] = bool(gathered["ok"])
             line["gathered"] = {"queries": gathered["queries"], "rows": gathered["rows"],
                                 "steps": S}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         obs, pack, goal = queries[0]
         cpu_n = args.cpu_samples if not W["meshes"] else max(1000, args.cpu_samples // 10)
         line["cpu_baseline"] = cpu_baseline(obs, goal, cpu_n, step_seed(0), args.cpu_workers,
                                             mode, mass, meshes=pack,
                                             what=W["text"].split(",")[0] + " scene")
-    if rank == 0 and world == 1 and W.get("alt_batch") and not args.no_alt:
+    if args.full and rank == 0 and world == 1 and W.get("alt_batch") and not args.no_alt:
         # the same workload at SURVEY 8d's default batch, beside the headline's tuned batch
         # (the batch changes the tree: more, smaller rounds see fresher snapshots)
         alt = dict(W, batch=W["alt_batch"])

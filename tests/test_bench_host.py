@@ -43,6 +43,7 @@ class _FakeEngine:
     def plan_begin(self, start, goal, mode, mass, exec_time, max_nodes, max_batch, seed=0):
         from torque_constrained_motion_planning_amd import _lib
         self.n = max_nodes - 1
+        self.seed = seed
         with _FakeEngine.lock:
             _FakeEngine.seeds.append(seed)
         return _lib.PLAN_OK
@@ -65,6 +66,9 @@ class _FakeEngine:
         r.launches_nearest, r.launches_nn_scan = 4, 3
         r.goal_node, r.goal_cost, r.goal_depth = self.n // 2 - 1, 3.5, 4
         return r
+
+    def plan_tree(self, cap):  # rows marked with the seed of the plan this engine ran last
+        return (np.full((cap, 7), float(self.seed)), np.zeros(cap), np.arange(cap) - 1, cap)
 
     def plan_fetch(self, r):
         K = r.n_traj
@@ -108,9 +112,9 @@ def _run_bench(monkeypatch, capsys, argv):
 
 @pytest.mark.parametrize("pipe", [1, 2])
 def test_bench_pipelined_single_query_steps(monkeypatch, capsys, pipe):
-    line = _run_bench(monkeypatch, capsys, ["--workload", "c2", "--steps", "4", "--warmup", "1",
-                                            "--pipeline", str(pipe), "--fleet", "0",
-                                            "--no-cpu-baseline", "--no-alt"])
+    line = _run_bench(monkeypatch, capsys, ["--full", "--workload", "c2", "--steps", "4",
+                                            "--warmup", "1", "--pipeline", str(pipe), "--fleet",
+                                            "0", "--no-cpu-baseline", "--no-alt"])
     assert line["steps"] == 4 and line["value"] > 0
     assert line["config"]["pipelined_steps"] == pipe
     assert line["config"]["streams_per_gpu"] == pipe
@@ -136,9 +140,9 @@ def test_bench_fused_fleets(monkeypatch, capsys):
     """c4's default: a step's queries in fleets (fused rounds), `pipeline` fleets in flight,
     each on its own group of engines; every query still begins, finishes and is fetched on its
     own engine with its own seed."""
-    line = _run_bench(monkeypatch, capsys, ["--workload", "c4", "--queries", "6", "--steps", "2",
-                                            "--warmup", "1", "--pipeline", "2", "--fleet", "3",
-                                            "--no-cpu-baseline"])
+    line = _run_bench(monkeypatch, capsys, ["--full", "--workload", "c4", "--queries", "6",
+                                            "--steps", "2", "--warmup", "1", "--pipeline", "2",
+                                            "--fleet", "3", "--no-cpu-baseline"])
     c = line["config"]
     assert c["queries_per_step"] == 6 and c["fused_queries"] == 3
     assert c["streams_per_gpu"] == 6 and c["queries_in_flight"] == 6
@@ -155,8 +159,8 @@ def test_bench_fused_fleets(monkeypatch, capsys):
 def test_bench_single_query_fleets(monkeypatch, capsys):
     """c3's default: consecutive steps' queries (one per step, each its own seed) in fleets of
     `fleet`, `pipeline` fleets in flight; the one-query-at-a-time line rides beside it."""
-    line = _run_bench(monkeypatch, capsys, ["--workload", "c3", "--steps", "6", "--warmup", "1",
-                                            "--fleet", "4", "--pipeline", "2",
+    line = _run_bench(monkeypatch, capsys, ["--full", "--workload", "c3", "--steps", "6",
+                                            "--warmup", "1", "--fleet", "4", "--pipeline", "2",
                                             "--no-cpu-baseline", "--no-alt", "--no-sublines"])
     c = line["config"]
     assert c["fused_queries"] == 4 and c["queries_in_flight"] == 8 and c["streams_per_gpu"] == 8
@@ -172,9 +176,9 @@ def test_bench_single_query_fleets(monkeypatch, capsys):
 
 
 def test_bench_multi_query_pipeline(monkeypatch, capsys):
-    line = _run_bench(monkeypatch, capsys, ["--workload", "c4", "--queries", "3", "--steps", "2",
-                                            "--warmup", "1", "--pipeline", "2", "--fleet", "0",
-                                            "--no-cpu-baseline"])
+    line = _run_bench(monkeypatch, capsys, ["--full", "--workload", "c4", "--queries", "3",
+                                            "--steps", "2", "--warmup", "1", "--pipeline", "2",
+                                            "--fleet", "0", "--no-cpu-baseline"])
     assert line["config"]["queries_per_step"] == 3 and line["config"]["fused_queries"] == 1
     assert _FakeEngine.fused == []
     assert line["config"]["streams_per_gpu"] == 6  # 3 queries x 2 steps in flight
@@ -197,13 +201,13 @@ def test_bench_default_sublines(monkeypatch, capsys):
     small["c4"] = dict(small["c4"], queries=4, fleet=2, pipeline=2, samples=2000)
     small["c5"] = dict(small["c5"], meshes=2, samples=3000)
     monkeypatch.setattr(bench, "WORKLOADS", small)
-    line = _run_bench(monkeypatch, capsys, ["--steps", "2", "--warmup", "1", "--samples", "5000",
-                                            "--no-cpu-baseline", "--no-alt"])
+    line = _run_bench(monkeypatch, capsys, ["--full", "--steps", "2", "--warmup", "1",
+                                            "--samples", "5000", "--no-cpu-baseline", "--no-alt"])
     # --samples: not the default headline, so no sub-lines
     assert "config_c4" not in line and "config_c5" not in line
     small["c3"] = dict(small["c3"], samples=5000)
-    line = _run_bench(monkeypatch, capsys, ["--steps", "2", "--warmup", "1", "--c5-steps", "3",
-                                            "--no-cpu-baseline", "--no-alt"])
+    line = _run_bench(monkeypatch, capsys, ["--full", "--steps", "2", "--warmup", "1",
+                                            "--c5-steps", "3", "--no-cpu-baseline", "--no-alt"])
     q = line["quality"]
     assert q["queries"] == 2 and q["goal_rate"] == 1.0 and q["path_cost_mean"] == 3.5
     assert q["rounds_per_query"] == 4 and q["goal_depth_mean"] == 4
@@ -215,3 +219,87 @@ def test_bench_default_sublines(monkeypatch, capsys):
     assert c5["kernel_timing"].startswith("the timed steps")
     assert c5["roofline"]["avg_launch_ms"] > 0 and c5["quality"]["queries"] == 3
     assert "cpu_baseline" not in c4 and "config_alt" not in c5
+
+
+def test_bench_plain_run_is_lean(monkeypatch, capsys):
+    """Without --full the default command plans the warmup and the timed steps and nothing else:
+    no measured peaks, no per-kernel or one-at-a-time pass, no CPU baseline, default-batch line
+    or sub-lines; the headline fields stay."""
+    import bench
+    small = dict(bench.WORKLOADS)
+    small["c3"] = dict(small["c3"], samples=5000)
+    monkeypatch.setattr(bench, "WORKLOADS", small)
+    monkeypatch.setattr(_FakeEngine, "microbench", lambda self: pytest.fail("microbench ran"))
+    monkeypatch.setattr(bench, "cpu_baseline", lambda *a, **k: pytest.fail("CPU baseline ran"))
+    line = _run_bench(monkeypatch, capsys, ["--gpus", "1", "--steps", "6", "--warmup", "1"])
+    # c3's default: warmup 1 x 2 fleets of 4, then the 6 timed steps in two fleets of 3
+    assert sorted(_FakeEngine.fused) == [3, 3, 4, 4]
+    assert len(_FakeEngine.seeds) == 14 and len(set(_FakeEngine.seeds)) == 14
+    for k in ("cpu_baseline", "config_alt", "config_single_query", "config_c4", "config_c5",
+              "measured_peaks", "roofline", "kernel_ms_per_step", "kernel_timing"):
+        assert k not in line, k
+    assert line["steps"] == 6 and line["unit"] == "samples/s" and line["dtype"] == "f64"
+    assert line["higher_is_better"] is True and line["metric"].startswith("torque-feasible")
+    assert line["value"] == pytest.approx(6 * 5000 / (line["ms_per_step"] * 6e-3), rel=1e-6)
+    assert line["quality"]["queries"] == 6 and line["config"]["fused_queries"] == 4
+
+
+@pytest.mark.parametrize("argv, prefixes", [
+    (["--steps", "3", "--warmup", "0"], [""]),
+    (["--workload", "c4", "--queries", "3", "--steps", "2", "--warmup", "0"],
+     ["q00_", "q01_", "q02_"])])
+def test_bench_dump_outputs(monkeypatch, capsys, tmp_path, argv, prefixes):
+    """--dump-outputs: the last timed step's queries, one set of float64 .npy files per query --
+    the plan's outcome, the fetched arrays and, for a one-query step, the tree on the engine that
+    planned it (the fake's tree rows carry the plan's seed: c3's last step has 1234 + 2)."""
+    import bench
+    small = dict(bench.WORKLOADS)
+    small["c3"] = dict(small["c3"], samples=5000)
+    small["c4"] = dict(small["c4"], samples=2000)
+    monkeypatch.setattr(bench, "WORKLOADS", small)
+    one = len(prefixes) == 1
+    n = small["c3" if one else "c4"]["samples"]
+    _run_bench(monkeypatch, capsys, argv + ["--dump-outputs", str(tmp_path / "out")])
+    kinds = ("result", "waypoints", "q", "qd", "qdd", "psg", "tau") + (("tree",) if one else ())
+    names = [p + k for p in prefixes for k in kinds]
+    assert sorted(os.listdir(tmp_path / "out")) == sorted(x + ".npy" for x in names)
+    for p in prefixes:
+        got = {k: np.load(tmp_path / "out" / (p + k + ".npy")) for k in ("result", "q", "psg")}
+        assert all(a.dtype == np.float64 for a in got.values())
+        assert dict(zip(bench.OUTCOME_FIELDS, got["result"])) == dict(
+            status=0, goal_found=1, n_nodes=n // 2, n_samples=n, goal_node=n // 2 - 1,
+            n_waypoints=5, n_traj=40, goal_cost=3.5, goal_depth=4)
+        assert got["q"].shape == (40, 7) and got["psg"].shape == (40,)
+    if one:
+        tree = np.load(tmp_path / "out" / "tree.npy")
+        assert tree.dtype == np.float64 and tree.shape == (n // 2, 9)
+        assert (tree[:, 0] == 1236).all() and (tree[:, 8] == np.arange(n // 2) - 1).all()
+
+
+def test_bench_dump_outputs_sampled_and_unsolved(monkeypatch, tmp_path):
+    """The small arrays are written whole and one past its share of what is left of the size cap
+    is cut to the same seeded rows every time; a query without a path writes no path arrays, so
+    no file is ever empty."""
+    import bench
+    from torque_constrained_motion_planning_amd import _lib
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 3400)
+    r = _lib.PlanResult()
+    r.n_nodes = 6
+    eng = _FakeEngine()
+    eng.seed = 5
+    big = dict(waypoints=np.zeros((2, 7)), q=np.arange(700.0).reshape(100, 7), qd=np.zeros((3, 7)),
+               qdd=np.zeros((3, 7)), psg=np.arange(100.0), tau=np.zeros((3, 7)))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), [(r, big, eng), (r, None, eng)], trees=True)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(["q00_%s.npy" % k for k in list(big) + ["result", "tree"]] +
+                           ["q01_result.npy", "q01_tree.npy"])
+    assert all(np.load(tmp_path / "a" / f).size > 0 for f in files)
+    # result 2 x 72, waypoints 112, qd / qdd / tau 3 x 168, tree 2 x 432, psg 800 bytes: whole;
+    # 3400 less those 2424 leaves q 976 bytes, 17 rows of 56, in order
+    assert (np.load(tmp_path / "a" / "q00_psg.npy") == big["psg"]).all()
+    assert np.load(tmp_path / "a" / "q01_tree.npy").shape == (6, 9)
+    q = np.load(tmp_path / "a" / "q00_q.npy")
+    assert q.shape == (17, 7) and (np.diff(q[:, 0]) > 0).all()
+    assert (q == np.load(tmp_path / "b" / "q00_q.npy")).all()
+    assert sum(np.load(tmp_path / "a" / f).nbytes for f in files) <= 3400

@@ -4,7 +4,7 @@
 # stages:
 #   tests[=K]        pytest -m gpu (optionally -k K), then smoke()
 #   bench[=W]        bench.py line for workload W (c3 default), 5 steps (c5: 2)
-#   default          the driver's own default command, `python bench.py` (C3, CPU baseline too)
+#   default          the whole measurement, `python bench.py --full` (C3, CPU baseline, sub-lines)
 #   trace[=W]        rocprofv3 --kernel-trace --stats of the same bench command
 #   pmc[=W]          PMC passes FETCH_SIZE / WRITE_SIZE (one run each) over one bench step
 #   sq[=W]           PMC pass of SQ wave / busy counters over one bench step
@@ -40,17 +40,17 @@ agg() {  # PASS_DIR -> PASS_DIR.json (per-kernel totals), raw CSVs removed (gpur
 }
 pmc_args() {  # workload -> bench.py arguments of a counter pass: whole fleets, one in flight
   case "$1" in
-    c3|"") echo "--steps 4 --warmup 0 --pipeline 1 --no-sublines" ;;   # one fleet of 4 (+ the timing pass's)
-    c2) echo "--workload c2 --steps 8 --warmup 0 --pipeline 1" ;;
-    c5) echo "--workload c5 --steps 3 --warmup 0 --pipeline 1 --no-single" ;;   # one fleet of 3
-    *) echo "--workload $1 --steps 1 --warmup 0 --pipeline 1" ;;
+    c3|"") echo "--full --steps 4 --warmup 0 --pipeline 1 --no-sublines" ;;   # one fleet of 4 (+ the timing pass's)
+    c2) echo "--full --workload c2 --steps 8 --warmup 0 --pipeline 1" ;;
+    c5) echo "--full --workload c5 --steps 3 --warmup 0 --pipeline 1 --no-single" ;;   # one fleet of 3
+    *) echo "--full --workload $1 --steps 1 --warmup 0 --pipeline 1" ;;
   esac
 }
 bench_args() {  # workload -> bench.py arguments of one measured line
   case "$1" in
-    c5) echo "--workload c5 --steps 2 --warmup 1" ;;
-    c3|"") echo "--steps 5 --warmup 1 --no-sublines" ;;
-    *) echo "--workload $1 --steps 5 --warmup 1" ;;
+    c5) echo "--full --workload c5 --steps 2 --warmup 1" ;;
+    c3|"") echo "--full --steps 5 --warmup 1 --no-sublines" ;;
+    *) echo "--full --workload $1 --steps 5 --warmup 1" ;;
   esac
 }
 for st in "$@"; do
@@ -67,7 +67,7 @@ for st in "$@"; do
       w=${arg:-c3}
       timeout -k 10 300 python -u bench.py $(bench_args $w) > $O/bench_$w.json 2> $O/bench_$w.err ;;
     default)
-      timeout -k 10 600 python -u bench.py > $O/bench_default.json 2> $O/bench_default.err ;;
+      timeout -k 10 600 python -u bench.py --full > $O/bench_default.json 2> $O/bench_default.err ;;
     trace)
       w=${arg:-c3}
       timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/trace_$w -o run --output-format csv \
@@ -130,13 +130,13 @@ for st in "$@"; do
       IFS=',' read -ra cfgs <<< "${arg#*:}"
       for fp in "${cfgs[@]}"; do
         f=${fp%/*}; p=${fp#*/}
-        timeout -k 10 600 python -u bench.py --workload $w --steps $n --warmup 1 --fleet $f --pipeline $p \
+        timeout -k 10 600 python -u bench.py --full --workload $w --steps $n --warmup 1 --fleet $f --pipeline $p \
           --no-cpu-baseline --no-alt --no-sublines > $O/sweep_${w}_f${f}_p${p}.json 2> $O/sweep_${w}_f${f}_p${p}.err
       done ;;
     line)
       w=${arg%%:*}; extra=${arg#*:}; [ "$extra" = "$arg" ] && extra=""
       nl=$(ls $O 2>/dev/null | grep -c "^line_${w}_" || true)
-      timeout -k 10 600 python -u bench.py --workload $w ${extra//,/ } > $O/line_${w}_$nl.json 2> $O/line_${w}_$nl.err ;;
+      timeout -k 10 600 python -u bench.py --full --workload $w ${extra//,/ } > $O/line_${w}_$nl.json 2> $O/line_${w}_$nl.err ;;
     abw)
       bash tools/ab_lib.sh $TAG/ab_$arg "${AB_LIBS:?env:AB_LIBS=...}" --workload $arg --no-sublines ${AB_ARGS:-} ;;
     abenv)
