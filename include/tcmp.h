@@ -155,6 +155,39 @@ int tcmp_check_edges(tcmp_handle* h, const double* from, const double* to, int64
                      const double* resolutions, int32_t torque_mode, double payload_mass,
                      int32_t* n_safe, int32_t* n_steps, double* last);
 
+/* Force-aware path shortcutting (no reference counterpart: the reference returns
+ * goal_n.retrace() as it is).  One pass: anchors a_k = min(k s, n - 1) with s = 1 when
+ * n <= max_anchors, else ceil((n - 1) / (max_anchors - 1)); every chord between two anchors at
+ * least two waypoints apart goes through tcmp_check_edges' check and is valid when its whole
+ * extend is safe and ends within 1e-6 of its target (the rewire acceptance, rrt_star.py:191);
+ * a dynamic program over the anchors (original hops as they are, valid chords at their
+ * distance fn length; the original hop wins ties, then the lowest anchor) picks the cheapest
+ * subsequence; chosen chords are replaced by their extend points, ending in the target waypoint
+ * itself.  Passes repeat on the new list until one uses no chord.  First and last waypoint are
+ * kept bit for bit and cost_after <= cost_before.  Deterministic. */
+typedef struct {
+  int32_t max_anchors;       /* 2..1024, 0 = 512 */
+  int32_t passes;            /* 1..8, 0 = 1 */
+} tcmp_shortcut_cfg;
+
+typedef struct {
+  int32_t status;            /* 0, or TCMP_PLAN_NO_GOAL when the open plan has no goal node */
+  int32_t passes_run;
+  int64_t n_before, n_after; /* waypoints */
+  double cost_before, cost_after; /* summed distance fn over consecutive waypoints */
+  int64_t n_anchors;         /* first pass */
+  uint64_t chords_tested, chords_valid, chords_used, chord_steps; /* over all passes */
+  double ms;                 /* device time of the stage (0 with timing off) */
+} tcmp_shortcut_result;
+
+/* shortcut n_wp waypoints (n_wp x 7; 1 or 2 come back as they are) in the scene set on the
+ * handle.  resolutions (7, NULL = 0.1), weights (7, NULL = 10): the extend and distance fns'.
+ * out: cap_out x 7; too small: status -4 with res->n_after set.  Leaves an open plan alone. */
+int tcmp_shortcut_path(tcmp_handle* h, const double* waypoints, int64_t n_wp,
+                       const double* resolutions, const double* weights, int32_t torque_mode,
+                       double payload_mass, const tcmp_shortcut_cfg* cfg, double* out,
+                       int64_t cap_out, tcmp_shortcut_result* res);
+
 /* argmin over tree nodes of the weighted distance (rrt_star.py:9-14,171), first index wins
  * ties.  tree: T x 7, samples: n x 7, weights: 7 positive (NULL = 10 = 1/radius).  Runs the
  * planner's own nearest path: the radix-tree cell index of the tree and the pruned exact
@@ -303,6 +336,14 @@ int tcmp_plan_finish(tcmp_handle* h, tcmp_plan_result* result);
  * No min-jerk, no validation: status is 0 (goal found) or TCMP_PLAN_NO_GOAL, n_traj 0,
  * first_fail -1; tcmp_plan_fetch then copies the waypoints. */
 int tcmp_plan_retrace(tcmp_handle* h, tcmp_plan_result* result);
+
+/* shortcut the open plan's path: retrace, then tcmp_shortcut_path's passes with the plan's own
+ * weights, resolutions, torque mode and payload mass; the shortened list stays in the engine, and
+ * the next tcmp_plan_finish / tcmp_plan_retrace / tcmp_plan_finish_many of this plan uses it
+ * instead of retracing (until the next tcmp_plan_begin).  goal_cost / goal_depth stay the
+ * tree's, and the plan's counters do not include the chords' (those are in `res`).  Without a
+ * goal node: res->status = TCMP_PLAN_NO_GOAL and nothing changes. */
+int tcmp_plan_shortcut(tcmp_handle* h, const tcmp_shortcut_cfg* cfg, tcmp_shortcut_result* res);
 
 /* copy the finished plan: waypoints (n_waypoints x 7), trajectory q/qd/qdd (n_traj x 7),
  * psg (n_traj), tau = Conf.torques without payload (n_traj x 7).  Any pointer may be NULL. */

@@ -36,6 +36,7 @@ EXPORTS = [
     "tcmp_rendezvous", "tcmp_dist_init", "tcmp_dist_destroy", "tcmp_dist_rank",
     "tcmp_dist_barrier", "tcmp_dist_allreduce", "tcmp_dist_allgather_i64", "tcmp_gather_paths",
     "tcmp_gather_layout", "tcmp_gather_pack", "tcmp_gather_unpack", "tcmp_dist_rccl_ranks",
+    "tcmp_shortcut_path", "tcmp_plan_shortcut",
 ]
 TRAJ_COLS = 22
 REDUCE_SUM, REDUCE_MAX = 0, 1
@@ -77,6 +78,27 @@ class PlanResult(ctypes.Structure):
         ("rewire_steps", ctypes.c_uint64), ("graph_launches", ctypes.c_int64),
         ("fused_plans", ctypes.c_int64), ("ms_edge_prep", ctypes.c_double),
         ("goal_cost", ctypes.c_double), ("goal_depth", ctypes.c_int64),
+    ]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+class ShortcutCfg(ctypes.Structure):
+    """tcmp_shortcut_cfg"""
+    _fields_ = [("max_anchors", ctypes.c_int32), ("passes", ctypes.c_int32)]
+
+
+class ShortcutResult(ctypes.Structure):
+    """tcmp_shortcut_result"""
+    _fields_ = [
+        ("status", ctypes.c_int32), ("passes_run", ctypes.c_int32),
+        ("n_before", ctypes.c_int64), ("n_after", ctypes.c_int64),
+        ("cost_before", ctypes.c_double), ("cost_after", ctypes.c_double),
+        ("n_anchors", ctypes.c_int64),
+        ("chords_tested", ctypes.c_uint64), ("chords_valid", ctypes.c_uint64),
+        ("chords_used", ctypes.c_uint64), ("chord_steps", ctypes.c_uint64),
+        ("ms", ctypes.c_double),
     ]
 
     def as_dict(self):
@@ -169,6 +191,12 @@ def load_library(path=LIB_PATH):
             L.tcmp_gather_unpack.argtypes = [i32, _i64p, _i64p, _dp, ctypes.c_int64,
                                              ctypes.c_int64, _i64p, _i64p, _dp, _i64p, _i64p]
         L.tcmp_dist_rccl_ranks.argtypes = [vp, _i32p]
+        if hasattr(L, "tcmp_shortcut_path"):  # absent from A/B builds of older sources
+            L.tcmp_shortcut_path.argtypes = [vp, _dp, ctypes.c_int64, _dp, _dp, ctypes.c_int32,
+                                             ctypes.c_double, ctypes.POINTER(ShortcutCfg), _dp,
+                                             ctypes.c_int64, ctypes.POINTER(ShortcutResult)]
+            L.tcmp_plan_shortcut.argtypes = [vp, ctypes.POINTER(ShortcutCfg),
+                                             ctypes.POINTER(ShortcutResult)]
         _lib = L
         return L
 
@@ -356,6 +384,39 @@ class Engine:
                                             float(mass), ns.ctypes.data_as(_i32p),
                                             nt.ctypes.data_as(_i32p), _d(last)))
         return ns, nt, last
+
+    def shortcut_path(self, waypoints, torque_mode, payload_mass, resolutions=None, weights=None,
+                      max_anchors=512, passes=1):
+        """tcmp_shortcut_path: force-aware shortcutting of a waypoint list (n, 7) in the scene
+        set on this engine -> (waypoints, ShortcutResult)."""
+        if not hasattr(self.L, "tcmp_shortcut_path"):
+            raise TcmpError("tcmp_shortcut_path: not in this library build")
+        wp = _rows(waypoints, "waypoints")
+        res = None if resolutions is None else np.ascontiguousarray(resolutions, dtype=np.float64)
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
+        cfg = ShortcutCfg(int(max_anchors), int(passes))
+        r = ShortcutResult()
+        cap = len(wp)
+        while True:
+            out = np.zeros((max(cap, 1), 7))
+            rc = self.L.tcmp_shortcut_path(self.h, _d(wp), len(wp), _d(res), _d(w),
+                                           int(torque_mode), float(payload_mass),
+                                           ctypes.byref(cfg), _d(out), cap, ctypes.byref(r))
+            if rc == -4 and r.n_after > cap:  # a chord's extend points outnumber what it replaced
+                cap = int(r.n_after)
+                continue
+            self._check(rc)
+            return out[:r.n_after].copy(), r
+
+    def plan_shortcut(self, max_anchors=512, passes=1):
+        """tcmp_plan_shortcut: shortcut the open plan's path; the next plan_finish /
+        plan_retrace uses the shortened list."""
+        if not hasattr(self.L, "tcmp_plan_shortcut"):
+            raise TcmpError("tcmp_plan_shortcut: not in this library build")
+        cfg = ShortcutCfg(int(max_anchors), int(passes))
+        r = ShortcutResult()
+        self._check(self.L.tcmp_plan_shortcut(self.h, ctypes.byref(cfg), ctypes.byref(r)))
+        return r
 
     def nearest(self, tree, samples, weights=None):
         t = _rows(tree, "tree"); s = _rows(samples, "samples")

@@ -1362,6 +1362,15 @@ struct tcmp_handle {
   // blit kernels through pageable memory), sized at plan_begin for kcap rows
   void* fetch_pin = nullptr;
   size_t fetch_pin_n = 0;
+  // force-aware shortcutting (tcmp_shortcut.h): the second waypoint buffers, the chords' edge
+  // job, the pass's tables, the scratch state the chords' launch counts into; sc_live: the open
+  // plan's waypoint buffer holds a shortened list (tcmp_plan_shortcut) the finish must keep
+  DBuf<double> sc_wp[2], sc_from, sc_to, sc_last, sc_rec, sc_len, sc_orig;
+  DBuf<int> sc_nsafe, sc_nsteps;
+  DBuf<int2> sc_kl, sc_hops;
+  DBuf<unsigned char> sc_stats;
+  DevState* st_sc = nullptr;
+  bool sc_live = false;
   int edge_split = 4;  // most lanes per edge in small rounds (environment TCMP_EDGE_SPLIT=1/2/4)
   int edge_wps = 2;    // k_edges' persistent grid, blocks per CU (environment TCMP_EDGE_WPS=1/2)
 
@@ -2019,6 +2028,14 @@ int tcmp_destroy(tcmp_handle* h) {
   h->second.release();
   h->chain.release();
   h->u0.release();
+  for (auto* b : {&h->sc_wp[0], &h->sc_wp[1], &h->sc_from, &h->sc_to, &h->sc_last, &h->sc_rec,
+                  &h->sc_len, &h->sc_orig})
+    b->release();
+  for (auto* b : {&h->sc_nsafe, &h->sc_nsteps}) b->release();
+  h->sc_kl.release();
+  h->sc_hops.release();
+  h->sc_stats.release();
+  if (h->st_sc) (void)hipFree(h->st_sc);
   for (auto e : h->ev_rec) (void)hipEventDestroy(e);
   h->drop_graph();
   for (auto e : h->ev_pool) (void)hipEventDestroy(e);
@@ -2995,6 +3012,7 @@ int plan_begin_launch(tcmp_handle* h, const tcmp_plan_cfg* cfg, tcmp_plan_result
   }
   h->fin_W = 0;
   h->fin_K = 0;
+  h->sc_live = false;
   // one upload and one host wait: the handle's pinned block holds the start / goal rows, the
   // root, the plan state and parameters; k_plan_init scatters them on the device
   if (int rc2 = h->dpin.ensure(sizeof(tcmp_handle::Pin))) return rc2;
@@ -3636,9 +3654,11 @@ static int plan_finish_launch(tcmp_handle* h, tcmp_plan_result* r, bool traj) {
   // goal node) into the buffers tcmp_plan_begin sized, so the host waits once
   hipEvent_t e0;
   h->mark_begin(F_FINISH, &e0);
-  hipLaunchKernelGGL(k_retrace, dim3(1), dim3(256), 0, h->stream, h->dP, h->st,
-                     Tree{h->cfg.p, h->parent.p, h->tgt.p, h->meta.p}, h->chain.p, h->wp.p,
-                     (long long)(h->wp.n / 7));
+  // (after tcmp_plan_shortcut the waypoint buffer and the state hold the shortened list)
+  if (!h->sc_live)
+    hipLaunchKernelGGL(k_retrace, dim3(1), dim3(256), 0, h->stream, h->dP, h->st,
+                       Tree{h->cfg.p, h->parent.p, h->tgt.p, h->meta.p}, h->chain.p, h->wp.p,
+                       (long long)(h->wp.n / 7));
   if (traj) finish_launch_traj(h);
   HIPCHK(hipGetLastError());
   h->mark_end(F_FINISH, e0);
@@ -3934,3 +3954,4 @@ int tcmp_plan_debug_round(tcmp_handle* h, int64_t cap, double* cand, int32_t* nn
 }  // extern "C"
 
 #include "tcmp_fleet.h"
+#include "tcmp_shortcut.h"

@@ -51,14 +51,20 @@ def _radius_value(radius):
 
 def rrt_star_force_aware(start, goal, distance, sample, extend, collision, torque_fn, dynam_fn,
                          radius, max_time=INF, max_iterations=INF, goal_probability=.2,
-                         informed=False):
-    """rrt_star.py:151-211 -> (path, vels, accels, psg) or (None, None, None, None)."""
+                         informed=False, shortcut=False):
+    """rrt_star.py:151-211 -> (path, vels, accels, psg) or (None, None, None, None).
+    shortcut (no reference counterpart, off by default): force-aware shortcutting of the
+    retraced path on the device (Engine.plan_shortcut) before dynam_fn; engine loop only."""
     k = _kinds(distance, sample, extend, collision, torque_fn, dynam_fn)
     if k["distance"] and k["extend"] and k["collision"] and k["torque"]:
         res, _, _ = _rrt_engine(start, goal, distance, sample, extend, collision, torque_fn,
                                 dynam_fn, radius, max_iterations, goal_probability, k["dynam"],
-                                informed)
+                                informed, shortcut)
         return res
+    if shortcut:
+        raise NotImplementedError(
+            "shortcut=True needs the package's own distance, extend, collision and torque "
+            "callbacks (the chords are checked on the device)")
     return _rrt_host(start, goal, distance, sample, extend, collision, torque_fn, dynam_fn,
                      radius, max_time, max_iterations, goal_probability, informed, k)
 
@@ -112,7 +118,8 @@ def _finish(eng, dynam_fn=None, torque_fn=None):
 
 # ---- engine loop ---------------------------------------------------------------------------
 def _rrt_engine(start, goal, distance, sample, extend, collision, torque_fn, dynam_fn, radius,
-                max_iterations, goal_probability, native_dynam=True, informed=False):
+                max_iterations, goal_probability, native_dynam=True, informed=False,
+                shortcut=False):
     if max_iterations == INF:
         raise ValueError("max_iterations must be finite (the reference's time guard never "
                          "fires, rrt_star.py:159, so INF iterations never return)")
@@ -145,15 +152,19 @@ def _rrt_engine(start, goal, distance, sample, extend, collision, torque_fn, dyn
         if found and not goal_found and informed:
             goal_cost = eng.plan_goal()[1]
         goal_found = found
+    if shortcut:
+        eng.plan_shortcut()
     return _finish(eng, None if native_dynam else dynam_fn, torque_fn)
 
 
 def rrt_star_batched(start, goal, obstacles, torque_mode, payload_mass, execution_time,
                      n_samples, batch=65536, seed=0, weights=None, resolutions=None,
                      radius=0.01, goal_probability=0.2, device=0, engine=None,
-                     self_collisions=False):
+                     self_collisions=False, shortcut=False, shortcut_passes=1):
     """Engine-native batched frontier: n_samples Philox-drawn candidates, `batch` per round
     (self_collisions: the arm's self-collision pairs too, utils.py:3138-3149).
+    shortcut: force-aware shortcutting of the path (Engine.plan_shortcut, shortcut_passes
+    passes) between the rounds and the finish; its ShortcutResult is raw["shortcut"].
 
     Returns ((path, vels, accels, psg) | (None,)*4, PlanResult, raw arrays)."""
     from .scene import mesh_pack, obstacle_array
@@ -167,7 +178,13 @@ def rrt_star_batched(start, goal, obstacles, torque_mode, payload_mass, executio
     if st == _lib.PLAN_START_GOAL_COLLISION:
         return (None, None, None, None), None, None
     eng.plan_run(int(n_samples), int(batch))
-    return _finish(eng)
+    if not shortcut:
+        return _finish(eng)
+    sc = eng.plan_shortcut(passes=shortcut_passes)
+    res, r, raw = _finish(eng)
+    raw = dict(raw) if raw is not None else {}
+    raw["shortcut"] = sc
+    return res, r, raw
 
 
 # ---- host loop -------------------------------------------------------------------------------
