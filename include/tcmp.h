@@ -60,6 +60,21 @@ int tcmp_microbench(tcmp_handle* h, double* out);
  * centre(3), rotation R (9, row-major, columns = box axes, world frame), half extents(3). */
 int tcmp_set_scene(tcmp_handle* h, const double* obb, int32_t n_obs);
 
+/* Host only (no device): the interval tables the fused edge walk's first collision tier reads
+ * for a scene of n_obs <= 32 boxes (as tcmp_set_scene takes them), viewed at `cells` = 64, 128
+ * or 256 cells per axis.  tables [3][2][cells]: per axis, A[c] = bit mask of the boxes whose
+ * shrunk world-AABB upper bound reaches cell c's lower edge, then B[c] = those whose lower bound
+ * is at or below its upper edge.  bounds (may be NULL) [n_obs][8]: each box's fp32 bounds as the
+ * tier compares them (hi x y z, 0, -lo x y z, 0).  grid (may be NULL) [4]: the first cell's lower
+ * edge per axis, cells per metre.  No reference counterpart. */
+int tcmp_tier0_tables(const double* obb, int32_t n_obs, int32_t cells, float* bounds,
+                      uint32_t* tables, float* grid);
+
+/* Host only: the obstacle mask of each of n link boxes [lo, hi] ([n][3] each, fp32) from
+ * tcmp_tier0_tables' tables, computed as the device computes it. */
+int tcmp_tier0_masks(const uint32_t* tables, int32_t cells, const float* lo, const float* hi,
+                     int64_t n, uint32_t* masks);
+
 /* Fixed convex-mesh obstacles (replaces pybullet GEOM_MESH bodies in Problem.fixed: Bullet
  * collides the convex hull of the mesh vertices, utils.py:2833-2880, closest points with
  * distance = -0.04).  All in the world frame; n_mesh hulls, rows of mesh m are

@@ -6,6 +6,8 @@
 #   bench[=W]        bench.py line for workload W (c3 default), 5 steps (c5: 2)
 #   default          the whole measurement, `python bench.py --full` (C3, CPU baseline, sub-lines)
 #   trace[=W]        rocprofv3 --kernel-trace --stats of the same bench command
+#   rounds           kernel trace of C3 with one fleet at a time (--pipeline 1): k_fl_edges' launches
+#                    split by round (tools/edge_round_split.py)
 #   pmc[=W]          PMC passes FETCH_SIZE / WRITE_SIZE (one run each) over one bench step
 #   sq[=W]           PMC pass of SQ wave / busy counters over one bench step
 #   sq2[=W]          PMC pass of the issue-side SQ counters (WAIT_INST_ANY, ACTIVE_INST_ANY /
@@ -74,6 +76,11 @@ for st in "$@"; do
         -- python3 bench.py $(bench_args $w) --no-cpu-baseline --no-alt > $O/trace_$w.json 2> $O/trace_$w.err
       python3 tools/trace_split.py $O/trace_$w/run_kernel_trace.csv > $O/trace_split_$w.json
       cp $O/trace_$w/run_kernel_stats.csv $O/kernel_stats_$w.csv && rm -rf $O/trace_$w ;;
+    rounds)
+      timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/rounds -o run --output-format csv \
+        -- python3 bench.py --full --steps 8 --warmup 1 --pipeline 1 --no-sublines --no-cpu-baseline --no-alt > $O/rounds_bench.json 2> $O/rounds.err
+      python3 tools/edge_round_split.py $O/rounds/run_kernel_trace.csv > $O/edge_round_split.json
+      cp $O/rounds/run_kernel_stats.csv $O/kernel_stats_rounds.csv && rm -rf $O/rounds ;;
     pmc)
       w=${arg:-c3}; i=0
       for grp in FETCH_SIZE WRITE_SIZE; do

@@ -37,6 +37,7 @@ EXPORTS = [
     "tcmp_dist_barrier", "tcmp_dist_allreduce", "tcmp_dist_allgather_i64", "tcmp_gather_paths",
     "tcmp_gather_layout", "tcmp_gather_pack", "tcmp_gather_unpack", "tcmp_dist_rccl_ranks",
     "tcmp_shortcut_path", "tcmp_plan_shortcut",
+    "tcmp_tier0_tables", "tcmp_tier0_masks",
 ]
 TRAJ_COLS = 22
 REDUCE_SUM, REDUCE_MAX = 0, 1
@@ -197,6 +198,10 @@ def load_library(path=LIB_PATH):
                                              ctypes.c_int64, ctypes.POINTER(ShortcutResult)]
             L.tcmp_plan_shortcut.argtypes = [vp, ctypes.POINTER(ShortcutCfg),
                                              ctypes.POINTER(ShortcutResult)]
+        if hasattr(L, "tcmp_tier0_tables"):  # absent from A/B builds of older sources
+            _f32p, _u32p = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_uint32)
+            L.tcmp_tier0_tables.argtypes = [_dp, ctypes.c_int32, ctypes.c_int32, _f32p, _u32p, _f32p]
+            L.tcmp_tier0_masks.argtypes = [_u32p, ctypes.c_int32, _f32p, _f32p, ctypes.c_int64, _u32p]
         _lib = L
         return L
 

@@ -146,6 +146,44 @@ __device__ __forceinline__ double* wave_pose_slot(unsigned* wq) {
   return reinterpret_cast<double*>(wq + kQcap + 2);
 }
 
+// Tier 0 by interval tables (box scenes of at most 32 obstacles, the fused edge walk): two AABBs
+// overlap iff their intervals overlap on x, y and z, and on one axis the obstacles overlapping
+// a link interval [lo, hi] are {o: hi_o >= lo} & {o: lo_o <= hi} -- each set a function of one
+// scalar, so a table over the quantised coordinate returns it as a bit mask.  Per axis, over
+// kT0N uniform cells from t0_x0: A[c] = the obstacles whose upper bound reaches cell c's lower
+// edge, B[c] = those whose lower bound is at or below its upper edge; cell 0 extends to -inf
+// and the last cell to +inf, so a clamped index stays conservative.  The bounds are tier 0's
+// own (tier0_bounds: kPen-shrunk, margin-padded), so a link's mask holds every obstacle the
+// six compares would pass, plus those within one cell of passing (phase A drops these again:
+// each candidate is confirmed with the six compares before it is queued).
+// Master tables: u32 [3][2][kT0N] (A then B per axis).  A kernel with less LDS stages a
+// coarser view of n = kT0N / r cells: A_n[c] = A[c r], B_n[c] = B[c r + r - 1].
+constexpr int kT0N = 256;            // master cells per axis: 1 cm
+constexpr float kT0Range = 2.56f;    // metres per axis: the arm's reach (< 1.2 m) and margin
+constexpr int kT0MaxObs = 32;
+// the first cell's lower edge per axis: x and y centred on the base, z from 0.9 m below it
+__host__ __device__ constexpr float t0_x0(int i) { return i == 2 ? -0.90f : -1.28f; }
+// fp32 rounding of a cell index computation, in metres (|x - x0| < 8: < 1e-6), which the
+// tables' edges give way by
+constexpr double kT0Guard = 2e-6;
+struct T0Tab {
+  const void* tab;  // this plan's staged tables [3][2][n], u16 or u32 entries
+  float inv;        // cells per metre, n / kT0Range
+  int n;
+  int w32;          // 32-bit entries (some plan of the launch has more than 16 obstacles)
+};
+__host__ __device__ __forceinline__ int t0_cell(float x, float x0, float inv, int n) {
+  return (int)fminf(fmaxf((x - x0) * inv, 0.f), (float)(n - 1));
+}
+// master-table cell that cell c of an n-cell view reads (which: 0 for A, 1 for B)
+__host__ __device__ __forceinline__ int t0_master_cell(int which, int c, int n) {
+  const int r = kT0N / n;
+  return c * r + (which ? r - 1 : 0);
+}
+__host__ __device__ constexpr unsigned t0_plan_bytes(int n, int w32) {
+  return 6u * (unsigned)n * (w32 ? 4u : 2u);
+}
+
 // Obstacle records and the fp32 hull geometry are staged in LDS by every kernel that runs
 // collision checks (dynamic shared memory, stage_lds_bytes(n) per block): the per-(link,
 // obstacle) loop then reads LDS broadcasts instead of waiting on a global load per obstacle,
@@ -1516,10 +1554,13 @@ __device__ __forceinline__ int sphere_cert(int link, const float R[9], const flo
 // are compiled out, which keeps the box-only kernels' register allocation unchanged.
 // The joint-limit test (inclusive, utils.py:3181-3182) is the caller's: `active` lanes are
 // those within the limits that still need their obstacle (and self) pairs.
-template <bool MESH>
+// TAB = true (box scenes only): tier 0 reads the interval tables `tb` instead of comparing every
+// link box with every obstacle box; sc.obs32 is read only to confirm the tables' candidates.
+template <bool MESH, bool TAB = false>
 __device__ __forceinline__ bool collides_wave(const double cq[7], const double sq[7],
                                               bool active, const Scene sc, const Geo g,
-                                              StepStats& st) {
+                                              StepStats& st, const T0Tab tb = T0Tab{}) {
+  static_assert(!(MESH && TAB), "the interval tables serve box scenes");
   bool coll = false;
   if (sc.n_obs == 0 && !(MESH && sc.self_coll)) return coll;
   const int lane = lane_id();
@@ -1693,6 +1734,160 @@ __device__ __forceinline__ bool collides_wave(const double cq[7], const double s
   // A queue that fills up is flushed after the loop and phase A resumes at (o_res, l_res);
   // the link AABBs are rebuilt on resume, so nothing of phase A is live across a flush.
   int o_res = 0, l_res = 0;
+  if constexpr (TAB) {
+    // a link's world AABB (centre, half extent) from its frame
+    auto link_aabb = [&](int link, const double Rr[9], const double pr[3], double wc[3],
+                         double aabb[3]) {
+      if (link >= 7) {
+        // the hand and fingers: their hulls' boxes in their own frames (U = R: no axis
+        // products; as tight as their OBBs, which are within 4 degrees of the frame axes)
+        const double* b = kT0Box[link - 7];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+          wc[i] = Rr[3 * i + 0] * b[0] + Rr[3 * i + 1] * b[1] + Rr[3 * i + 2] * b[2] + pr[i];
+          aabb[i] = b[3] * fabs(Rr[3 * i + 0]) + b[4] * fabs(Rr[3 * i + 1]) + b[5] * fabs(Rr[3 * i + 2]);
+        }
+      } else {
+        double U[9];
+        link_obb(link, Rr, pr, wc, U, aabb);
+      }
+    };
+    // the ten link frames, generated incrementally; put(link, R, p) takes each as it is known
+    // (the table-less loop's chain below, kept apart: sharing it moved that loop's registers)
+    auto link_frames = [&](auto&& put) {
+      {
+        double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, p[3] = {0, 0, 0};
+#pragma unroll
+        for (int j = 0; j < 7; ++j) {
+          // (cos(alpha) as an exact 0, as in the table-less chain below)
+          const double cr = j > 0 ? 0.0 : kJcr[j], sr = kJsr[j],
+                       c = MESH ? stash[j * 64 + lane] : cq[j],
+                       s = MESH ? stash[(7 + j) * 64 + lane] : sq[j];
+          const double Rl[9] = {c, -s, 0.0, zmul(cr, s), zmul(cr, c), -sr, zmul(sr, s), zmul(sr, c), cr};
+          const double t[3] = {kJx[j], kJy[j], kJz[j]};
+          TCMP_FSA(R, p, Rl, t);
+          put(j, R, p);
+        }
+        const double I[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+        const double tz[3] = {0, 0, kFlangeZ};
+        TCMP_FSA(R, p, I, tz);
+        const double Rz[9] = {kHandCy, -kHandSy, 0, kHandSy, kHandCy, 0, 0, 0, 1};
+        const double z0[3] = {0, 0, 0};
+        TCMP_FSA(R, p, Rz, z0);
+        put(7, R, p);
+        double Rf[9], pf[3];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) Rf[k] = R[k];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) pf[k] = p[k];
+        const double tl[3] = {0, kFingerOpen, kFingerZ};
+        TCMP_FSA(Rf, pf, I, tl);
+        put(8, Rf, pf);
+        const double tr[3] = {0, -kFingerOpen, kFingerZ};
+        TCMP_FSA(R, p, I, tr);
+        put(9, R, p);
+      }
+    };
+    // Tier 0 by the interval tables: each link's obstacle mask is formed as its frame comes out
+    // of the chain (six cell indices, six LDS reads, five ANDs) and only the masks stay live.
+    // They survive a flush, so the frames are generated once per step and a full queue resumes
+    // at (link l_res, obstacle bit o_res).
+    unsigned lmask[10];
+    const unsigned char* const tab = static_cast<const unsigned char*>(tb.tab);
+    link_frames([&](int link, const double Rr[9], const double pr[3]) {
+      double wc[3], aabb[3];
+      link_aabb(link, Rr, pr, wc, aabb);
+      int ia[3], ib[3];
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        // the link's bounds as the six compares take them: fp32, with the rounding margin
+        const float c = (float)wc[i], h = (float)aabb[i] + 1e-5f;
+        ia[i] = t0_cell(c - h, t0_x0(i), tb.inv, tb.n) + 2 * i * tb.n;
+        ib[i] = t0_cell(c + h, t0_x0(i), tb.inv, tb.n) + (2 * i + 1) * tb.n;
+      }
+      unsigned m;
+      if (tb.w32) {
+        const unsigned* t = reinterpret_cast<const unsigned*>(tab);
+        m = t[ia[0]] & t[ib[0]] & t[ia[1]] & t[ib[1]] & t[ia[2]] & t[ib[2]];
+      } else {
+        const unsigned short* t = reinterpret_cast<const unsigned short*>(tab);
+        m = (unsigned)(t[ia[0]] & t[ib[0]] & t[ia[1]] & t[ib[1]] & t[ia[2]] & t[ib[2]]);
+      }
+      m = live ? m : 0u;
+      // The tables hold every obstacle the six compares pass plus those within one cell of
+      // passing.  The few candidates (most steps: none on any lane) are confirmed with the six
+      // compares themselves on the obstacle's fp32 record, the table-less loop's arithmetic to
+      // the bit, so the queue holds exactly the pairs that loop queues.
+      if (__ballot(m != 0u)) {
+        float lo[3], nhi[3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+          const float c = (float)wc[i], h = (float)aabb[i] + 1e-5f;
+          lo[i] = c - h;
+          nhi[i] = -(c + h);
+        }
+        unsigned rem = m;
+        while (rem) {
+          const int o = __builtin_ctz(rem);
+          rem &= rem - 1u;
+          const float4 oa = *reinterpret_cast<const float4*>(sc.obs32 + 8 * o);
+          const float4 ob4 = *reinterpret_cast<const float4*>(sc.obs32 + 8 * o + 4);
+          const float mx = fmaxf(fmaxf(lo[0] - oa.x, lo[1] - oa.y), lo[2] - oa.z),
+                      my = fmaxf(fmaxf(nhi[0] - ob4.x, nhi[1] - ob4.y), nhi[2] - ob4.z);
+          if (!((__float_as_uint(mx) & __float_as_uint(my)) >> 31)) m &= ~(1u << o);
+        }
+      }
+      lmask[link] = m;
+    });
+    // the links with a "maybe" on some lane (usually none, or one or two of the ten)
+    unsigned any = 0;
+#pragma unroll
+    for (int l = 0; l < 10; ++l) any |= lmask[l];
+    unsigned ul = 0;
+    if (__ballot(any != 0u)) {
+      unsigned lnz = 0;
+#pragma unroll
+      for (int l = 0; l < 10; ++l) lnz |= (unsigned)(lmask[l] != 0u) << l;
+      ul = wave_or_u32(lnz);
+    }
+    while (true) {
+      // link-major: per link the wave's OR of the lanes' masks, then a wave-uniform walk over
+      // its set bits, queueing (lane, link, obstacle)
+      bool full = false;
+      unsigned wl = ul & ~((1u << l_res) - 1u);
+#pragma unroll 1
+      while (wl && !full) {
+        const int l = __builtin_ctz(wl);
+        wl &= wl - 1u;
+        unsigned lm = 0;
+#pragma unroll
+        for (int k = 0; k < 10; ++k) lm = l == k ? lmask[k] : lm;
+        if (l == l_res) lm &= ~((1u << o_res) - 1u);  // obstacles already queued before a flush
+        unsigned um = wave_or_u32(lm);
+#pragma unroll 1
+        while (um) {
+          const int o = __builtin_ctz(um);
+          um &= um - 1u;
+          const bool m = (lm >> o) & 1u;
+          const uint64_t bm = __ballot(m);
+          if (count + (int)__popcll(bm) > kQcap) {
+            l_res = l;
+            o_res = o;
+            full = true;
+            break;
+          }
+          if (m) queue[count + (int)__popcll(bm & ((1ull << lane) - 1ull))] =
+              (unsigned)lane | ((unsigned)l << 6) | ((unsigned)o << 10);
+          count += (int)__popcll(bm);
+        }
+      }
+      if (count) flush();
+      if (!full) break;
+    }
+    __builtin_amdgcn_wave_barrier();
+    coll |= active && ((*cmask >> lane) & 1ull);
+    return coll;
+  }
   while (true) {
     // world AABBs of the 10 links in fp32 (centre, half extent + rounding margin)
     float bc[10][3], bh[10][3];

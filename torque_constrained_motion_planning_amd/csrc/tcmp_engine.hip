@@ -1240,6 +1240,8 @@ struct tcmp_handle {
   DBuf<double> verts, planes, edges;
   DBuf<double> obs;
   DBuf<float> obs32;
+  DBuf<unsigned> t0tab;    // tier 0's master interval tables [3][2][kT0N] (tier0_tables)
+  bool t0tab_ok = false;   // the scene has them: boxes only, at most kT0MaxObs
   DBuf<float> verts32, planes32;
   DBuf<unsigned short> eidx;
   int n_obs = 0;
@@ -1979,6 +1981,7 @@ int tcmp_destroy(tcmp_handle* h) {
   h->geo_ev.release();
   h->sph.release();
   h->obs32.release();
+  h->t0tab.release();
   h->mrange.release();
   for (auto* b : {&h->mib, &h->mv64, &h->mp64, &h->me64, &h->base_geo, &h->base_pd}) b->release();
   for (auto* b : {&h->mv32, &h->mp32, &h->me32, &h->mcl, &h->lcl[0], &h->lcl[1]}) b->release();
@@ -2383,6 +2386,40 @@ static void tier0_bounds(float* f, int i, double c, double Hs) {
   f[7] = 0.f;
 }
 
+// fp32 tier-0 record of box record d (c, B, h): its world AABB, kPen-shrunk
+static void tier0_box_record(const double* d, float* f) {
+  for (int i = 0; i < 3; ++i) {
+    const double H = fabs(d[3 + 3 * i]) * d[12] + fabs(d[4 + 3 * i]) * d[13] +
+                     fabs(d[5 + 3 * i]) * d[14];
+    tier0_bounds(f, i, d[i], H - kPen + 1e-5 + 1e-6 * (fabs(d[i]) + H));
+  }
+}
+
+// Tier 0's master interval tables of n <= kT0MaxObs obstacles from their tier-0 records t32
+// ([n][8]): tab[(2 axis + 0) kT0N + c] = A[c], the obstacles whose upper bound reaches cell c's
+// lower edge; tab[(2 axis + 1) kT0N + c] = B[c], those whose lower bound is at or below its upper
+// edge (tcmp_device.h).  Cell 0's lower edge is -inf and the last cell's upper edge +inf; every
+// edge gives way by kT0Guard, the rounding of a cell index computed in fp32.  An obstacle thinner
+// than 2 kPen on an axis has upper bound < lower bound there; it is entered like any other,
+// since the six compares pass it for a link interval that spans both bounds (and tier 1 may
+// pass it too: the link's extent counts towards the overlap).
+static void tier0_tables(const float* t32, int n, unsigned* tab) {
+  const double cell = (double)kT0Range / kT0N;
+  for (int i = 0; i < 3; ++i)
+    for (int c = 0; c < kT0N; ++c) {
+      const double lo_edge = c == 0 ? -INFINITY : (double)t0_x0(i) + c * cell - kT0Guard;
+      const double hi_edge = c == kT0N - 1 ? INFINITY : (double)t0_x0(i) + (c + 1) * cell + kT0Guard;
+      unsigned a = 0, b = 0;
+      for (int o = 0; o < n; ++o) {
+        const double hi = t32[8 * o + i], lo = -(double)t32[8 * o + 4 + i];
+        a |= (unsigned)(hi >= lo_edge) << o;
+        b |= (unsigned)(lo <= hi_edge) << o;
+      }
+      tab[(2 * i) * kT0N + c] = a;
+      tab[(2 * i + 1) * kT0N + c] = b;
+    }
+}
+
 int upload_scene(tcmp_handle* h) {
   const int n = h->n_box + h->n_mesh;
   const int n_self = h->self_coll ? TCMP_NLINKS : 0;
@@ -2397,12 +2434,7 @@ int upload_scene(tcmp_handle* h) {
                          R[2] == 0.0 && R[3] == 0.0 && R[5] == 0.0 && R[6] == 0.0 &&
                          R[7] == 0.0;
     d[15] = aligned ? 1.0 : 0.0;
-    float* f = t32.data() + 8 * o;
-    for (int i = 0; i < 3; ++i) {
-      const double H = fabs(d[3 + 3 * i]) * d[12] + fabs(d[4 + 3 * i]) * d[13] +
-                       fabs(d[5 + 3 * i]) * d[14];
-      tier0_bounds(f, i, d[i], H - kPen + 1e-5 + 1e-6 * (fabs(d[i]) + H));
-    }
+    tier0_box_record(d, t32.data() + 8 * o);
   }
   for (int m = 0; m < h->n_mesh; ++m) {
     const double* b = h->mesh_box.data() + 18 * m;
@@ -2430,24 +2462,36 @@ int upload_scene(tcmp_handle* h) {
   }
   if (int rc = h->obs.ensure(tmp.size())) return rc;
   if (int rc = h->obs32.ensure(t32.size())) return rc;
+  const bool tabs = h->n_mesh == 0 && !h->self_coll && n <= kT0MaxObs;
+  std::vector<unsigned> t0(tabs ? 6 * kT0N : 0);
+  if (tabs) {
+    tier0_tables(t32.data(), n, t0.data());
+    if (int rc = h->t0tab.ensure(t0.size())) return rc;
+  }
   // through the handle's pinned staging: the copies are queued and the call returns (a query's
   // set_scene no longer waits for the engine's stream); the staging is reused only after the
   // previous scene's copies have been done
-  const size_t b64 = tmp.size() * sizeof(double), b32 = t32.size() * sizeof(float);
+  const size_t b64 = tmp.size() * sizeof(double), b32 = t32.size() * sizeof(float),
+               bt0 = t0.size() * sizeof(unsigned);
   if (h->scene_ev) HIPCHK(hipEventSynchronize(h->scene_ev));
   else HIPCHK(hipEventCreateWithFlags(&h->scene_ev, hipEventDisableTiming));
-  if (h->scene_pin_n < b64 + b32) {
+  if (h->scene_pin_n < b64 + b32 + bt0) {
     if (h->scene_pin) HIPCHK(hipHostFree(h->scene_pin));
     h->scene_pin = nullptr;
     h->scene_pin_n = 0;
-    HIPCHK(hipHostMalloc(&h->scene_pin, b64 + b32));
-    h->scene_pin_n = b64 + b32;
+    HIPCHK(hipHostMalloc(&h->scene_pin, b64 + b32 + bt0));
+    h->scene_pin_n = b64 + b32 + bt0;
   }
   unsigned char* pin = static_cast<unsigned char*>(h->scene_pin);
   memcpy(pin, tmp.data(), b64);
   memcpy(pin + b64, t32.data(), b32);
   HIPCHK(hipMemcpyAsync(h->obs.p, pin, b64, hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipMemcpyAsync(h->obs32.p, pin + b64, b32, hipMemcpyHostToDevice, h->stream));
+  if (tabs) {
+    memcpy(pin + b64 + b32, t0.data(), bt0);
+    HIPCHK(hipMemcpyAsync(h->t0tab.p, pin + b64 + b32, bt0, hipMemcpyHostToDevice, h->stream));
+  }
+  h->t0tab_ok = tabs;
   HIPCHK(hipEventRecord(h->scene_ev, h->stream));
   h->n_obs = n;
   return 0;
@@ -2456,6 +2500,45 @@ int upload_scene(tcmp_handle* h) {
 }  // namespace
 
 extern "C" {
+
+int tcmp_tier0_tables(const double* obb, int32_t n_obs, int32_t cells, float* bounds,
+                      uint32_t* tables, float* grid) {
+  if (n_obs < 0 || n_obs > kT0MaxObs || (n_obs > 0 && !obb) || !tables)
+    return fail(-1, "tier-0 tables take 0..32 boxes");
+  if (cells != 64 && cells != 128 && cells != kT0N) return fail(-1, "cells: 64, 128 or 256");
+  std::vector<float> t32((size_t)std::max(n_obs, 1) * 8, 0.f);
+  for (int o = 0; o < n_obs; ++o) {
+    double d[16] = {0};
+    for (int k = 0; k < 15; ++k) d[k] = obb[15 * o + k];
+    tier0_box_record(d, t32.data() + 8 * o);
+  }
+  std::vector<unsigned> m(6 * kT0N);
+  tier0_tables(t32.data(), n_obs, m.data());
+  for (int ab = 0; ab < 6; ++ab)
+    for (int c = 0; c < cells; ++c)
+      tables[ab * cells + c] = m[ab * kT0N + t0_master_cell(ab & 1, c, cells)];
+  if (bounds) memcpy(bounds, t32.data(), (size_t)n_obs * 8 * sizeof(float));
+  if (grid) {
+    for (int i = 0; i < 3; ++i) grid[i] = t0_x0(i);
+    grid[3] = (float)cells / kT0Range;
+  }
+  return 0;
+}
+
+int tcmp_tier0_masks(const uint32_t* tables, int32_t cells, const float* lo, const float* hi,
+                     int64_t n, uint32_t* masks) {
+  if (!tables || !lo || !hi || !masks || n < 0) return fail(-1, "null argument");
+  if (cells != 64 && cells != 128 && cells != kT0N) return fail(-1, "cells: 64, 128 or 256");
+  const float inv = (float)cells / kT0Range;
+  for (int64_t j = 0; j < n; ++j) {
+    uint32_t m = ~0u;
+    for (int i = 0; i < 3; ++i)
+      m &= tables[(2 * i) * cells + t0_cell(lo[3 * j + i], t0_x0(i), inv, cells)] &
+           tables[(2 * i + 1) * cells + t0_cell(hi[3 * j + i], t0_x0(i), inv, cells)];
+    masks[j] = m;
+  }
+  return 0;
+}
 
 int tcmp_set_scene(tcmp_handle* h, const double* obb, int32_t n_obs) {
   TCMP_ENTER(h);

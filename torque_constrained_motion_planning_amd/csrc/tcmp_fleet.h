@@ -51,19 +51,27 @@ struct FleetPlan {
   int* ncount;
   Scene sc;           // box obstacles (obs, obs32, n_obs)
   int lds_obs;        // first row of this plan's obstacles in the fused k_edges' LDS
+  const unsigned* t0tab;  // tier 0's master interval tables (null: the scene has none)
 };
 
 // k_fl_edges' LDS: every plan's obstacle records (f64 [n][16], then f32 [n][8]), the hull
 // geometry, one pair queue per wave of a 512-thread block, and behind the queues each lane's
 // last safe configuration, [7][512] doubles (in LDS, not in 14 VGPRs: 80 -> 16 B of scratch
 // per lane, C3 fleet edges 3.25 -> 3.16 ms)
+//
+// With tier 0's interval tables (k_fl_edges<true>) every plan's tables, [3][2][t0n] entries of
+// 16 or 32 bits, follow everything else (behind the target columns when those are in LDS):
+// plan q's at q * t0_plan_bytes(t0n, w32).
 __host__ __device__ constexpr unsigned fleet_lds_bytes(int n_obs_total) {
   return scene_lds_bytes(n_obs_total) + geo_lds_bytes() + 8 * kQwaveBytes +
          7 * 512 * sizeof(double);
 }
+template <bool TAB>
 __device__ __forceinline__ void fleet_stage_lds(const FleetPlan* __restrict__ fp, int n_plans,
                                                 const Geo& g_g, double* lds, double** o64p,
-                                                float** o32p, Scene& so, Geo& go) {
+                                                float** o32p, Scene& so, Geo& go,
+                                                unsigned char* tabs = nullptr, int t0n = 0,
+                                                int w32 = 0) {
   const int tot = max(1, fp[n_plans - 1].lds_obs + fp[n_plans - 1].sc.n_obs);
   double* o64 = lds;
   float* o32 = reinterpret_cast<float*>(lds + 16 * tot);
@@ -78,6 +86,17 @@ __device__ __forceinline__ void fleet_stage_lds(const FleetPlan* __restrict__ fp
     const float* s32 = fp[q].sc.obs32;
     for (int i = threadIdx.x; i < n * 16; i += blockDim.x) o64[16 * off + i] = s64[i];
     for (int i = threadIdx.x; i < n * 8; i += blockDim.x) o32[8 * off + i] = s32[i];
+    if (TAB) {
+      // this plan's view of its master tables: entry e = (axis, A or B, cell)
+      const unsigned* mt = fp[q].t0tab;
+      unsigned char* dst = tabs + (size_t)q * t0_plan_bytes(t0n, w32);
+      for (int e = threadIdx.x; e < 6 * t0n; e += blockDim.x) {
+        const int ab = e / t0n, c = e - ab * t0n;
+        const unsigned v = mt[ab * kT0N + t0_master_cell(ab & 1, c, t0n)];
+        if (w32) reinterpret_cast<unsigned*>(dst)[e] = v;
+        else reinterpret_cast<unsigned short*>(dst)[e] = (unsigned short)v;
+      }
+    }
   }
   for (int i = threadIdx.x; i < TCMP_TOTAL_PLANES; i += blockDim.x) pl[i] = g_g.planes32[i];
   for (int i = threadIdx.x; i < 3 * TCMP_TOTAL_VERTS; i += blockDim.x) vt[i] = g_g.verts32[i];
@@ -265,14 +284,31 @@ __global__ __launch_bounds__(256) void k_fl_edge_records(const FleetPlan* __rest
 // per C3 launch (same-box A/B, profiles/r9w_ab_fetch/; reserving 16 work slots per counter
 // atomic instead of a step's need measured no change and is not kept)
 __host__ __device__ constexpr unsigned fleet_q2_bytes() { return 7u * 512u * sizeof(double); }
+// TAB: tier 0 by every plan's interval tables (t0n cells per axis, 32-bit entries if w32), staged
+// at byte tab_off of the LDS; without them (a scene of more than kT0MaxObs obstacles, or no room
+// in LDS) tier 0 compares each link box with each obstacle's fp32 record.
+// (the table-less kernel's argument list stays what it was: FleetT0<false> is empty)
+template <bool TAB> struct FleetT0 {};
+template <> struct FleetT0<true> {
+  unsigned tab_off;
+  int t0n, w32;
+};
+template <bool TAB>
 __global__ __launch_bounds__(512, 1) void k_fl_edges(const FleetPlan* __restrict__ fp, int K, int nb,
-                                                     Geo g_g, int q2lds) {
+                                                     Geo g_g, int q2lds, FleetT0<TAB> t0) {
   extern __shared__ double tcmp_lds[];
   Scene s0{};
   Geo g;
   double* o64;
   float* o32;
-  fleet_stage_lds(fp, K, g_g, tcmp_lds, &o64, &o32, s0, g);
+  unsigned char* tabs = nullptr;
+  int t0n = 0, w32 = 0;
+  if constexpr (TAB) {
+    tabs = reinterpret_cast<unsigned char*>(tcmp_lds) + t0.tab_off;
+    t0n = t0.t0n;
+    w32 = t0.w32;
+  }
+  fleet_stage_lds<TAB>(fp, K, g_g, tcmp_lds, &o64, &o32, s0, g, tabs, t0n, w32);
   const int lane = lane_id();
   const int waves = gridDim.x * (blockDim.x >> 6);
   int plan = (int)((long long)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * K / waves);
@@ -389,7 +425,13 @@ __global__ __launch_bounds__(512, 1) void k_fl_edges(const FleetPlan* __restrict
     sc.obs = o64 + 16 * F->lds_obs;
     sc.obs32 = o32 + 8 * F->lds_obs;
     sc.n_obs = F->sc.n_obs;
-    const bool coll = collides_wave<false>(cq, sq, active && !lim && tok, sc, g, ss) || lim;
+    bool coll;
+    if constexpr (TAB) {
+      const T0Tab tb{tabs + (size_t)plan * t0_plan_bytes(t0n, w32), (float)t0n / kT0Range, t0n, w32};
+      coll = collides_wave<false, true>(cq, sq, active && !lim && tok, sc, g, ss, tb) || lim;
+    } else {
+      coll = collides_wave<false>(cq, sq, active && !lim && tok, sc, g, ss) || lim;
+    }
     const bool ok = active && !coll && tok;
     steps += (unsigned)__popcll(__ballot(active));
     if (active) {
@@ -556,9 +598,26 @@ struct Fleet {
   int lds_obs;             // obstacles over all plans (the fused k_edges' LDS)
   int max_obs;             // the largest plan scene (k_fl_rewire_apply's LDS)
   bool mesh;               // mesh scenes: every plan's scene is the lead's
+  bool t0tabs;             // every plan's scene has tier 0's interval tables
+  int t0w32;               // their entries in LDS: 32 bits (some scene has > 16 boxes) or 16
   FleetPlan* fp;           // device descriptors
   FleetNN* fnn;
 };
+
+// Cells per axis of the interval tables k_fl_edges stages for this fleet: the finest of 256
+// (1 cm), 128 and 64 (4 cm) whose K tables fit in what the launch leaves of kFleetLdsCap, or 0
+// (the table-less kernel).  TCMP_T0_CELLS caps it (0: never the tables; for A/B runs).
+int fleet_t0_cells(const Fleet& F, int q2lds) {
+  if (!F.t0tabs) return 0;
+  static const int cap = [] {
+    const char* e = getenv("TCMP_T0_CELLS");
+    return e ? atoi(e) : kT0N;
+  }();
+  const unsigned used = fleet_lds_bytes(F.lds_obs) + (q2lds ? fleet_q2_bytes() : 0u);
+  for (int n = kT0N; n >= 64; n >>= 1)
+    if (n <= cap && used + F.K * t0_plan_bytes(n, F.t0w32) <= kFleetLdsCap) return n;
+  return 0;
+}
 
 int fleet_round(const Fleet& F, int nb, long long base) {
   tcmp_handle* h = F.h;
@@ -673,11 +732,17 @@ int fleet_round(const Fleet& F, int nb, long long base) {
                        lds_bytes(h), h->stream, F.fp, K, nb, h->scene(), h->geo());
   } else {
     const long long blocks = std::min<long long>(h->cu_count, ((long long)K * nb + 511) / 512);
-    const unsigned lds = fleet_lds_bytes(F.lds_obs);
-    const int q2lds = lds + fleet_q2_bytes() <= kFleetLdsCap;
-    hipLaunchKernelGGL(k_fl_edges, dim3((unsigned)std::max<long long>(1, blocks)), dim3(512),
-                       lds + (q2lds ? fleet_q2_bytes() : 0u), h->stream, F.fp, K, nb, h->geo(),
-                       q2lds);
+    // (the target columns come first: the tables never displace them)
+    const int q2lds = fleet_lds_bytes(F.lds_obs) + fleet_q2_bytes() <= kFleetLdsCap;
+    const int t0n = fleet_t0_cells(F, q2lds);
+    const unsigned lds = fleet_lds_bytes(F.lds_obs) + (q2lds ? fleet_q2_bytes() : 0u);
+    const dim3 eg((unsigned)std::max<long long>(1, blocks));
+    if (t0n)
+      hipLaunchKernelGGL(k_fl_edges<true>, eg, dim3(512), lds + K * t0_plan_bytes(t0n, F.t0w32),
+                         h->stream, F.fp, K, nb, h->geo(), q2lds, FleetT0<true>{lds, t0n, F.t0w32});
+    else
+      hipLaunchKernelGGL(k_fl_edges<false>, eg, dim3(512), lds, h->stream, F.fp, K, nb, h->geo(),
+                         q2lds, FleetT0<false>{});
   }
   HIPCHK(hipGetLastError());
   const hipEvent_t ee = h->mark_end(F_EDGES, ek);
@@ -720,7 +785,8 @@ bool same_scene(const tcmp_handle* a, const tcmp_handle* b) {
 // set by one thread could be lowered by another's smaller fleet before the first one launches.
 int fleet_lds_limits() {
   const struct { const void* k; unsigned b; } lim[] = {
-      {(const void*)k_fl_edges, kFleetLdsCap},
+      {(const void*)k_fl_edges<false>, kFleetLdsCap},
+      {(const void*)k_fl_edges<true>, kFleetLdsCap},
       {(const void*)k_fl_rewire_apply<false>, stage_lds_bytes(kMaxObstacles)},
       {(const void*)k_fl_edges_mesh, stage_lds_bytes_lean(kMaxObstacles)},
       {(const void*)k_fl_rewire_apply<true>, stage_lds_bytes_lean(kMaxObstacles)}};
@@ -772,6 +838,9 @@ int tcmp_plan_run_fused(tcmp_handle* const* hs, int32_t n, int64_t n_samples, in
   F.lds_obs = tot;
   F.max_obs = mx;
   F.mesh = h->mesh_kernels();
+  F.t0tabs = !F.mesh;
+  for (int q = 0; q < n; ++q) F.t0tabs = F.t0tabs && hs[q]->t0tab_ok;
+  F.t0w32 = mx > 16;
   if (!F.mesh && fleet_lds_bytes(tot) > kFleetLdsCap)
     return fail(-1, "too many obstacles over the fleet's scenes for the fused edge kernel");
   // the fleet index lives in the lead engine's index buffers (its own plan uses none of them
@@ -813,6 +882,7 @@ int tcmp_plan_run_fused(tcmp_handle* const* hs, int32_t n, int64_t n_samples, in
     f.ncount = e->ncount.p;
     f.sc = e->scene();
     f.lds_obs = lds_off;
+    f.t0tab = e->t0tab_ok ? e->t0tab.p : nullptr;
     lds_off += e->n_obs;
     hp[q] = f;
     hn[q] = FleetNN{e->cand.p, e->nn.p, e->second.p, e->nnscore.p, e->st, 0, 0};
