@@ -163,6 +163,44 @@ int tcmp_check_body(tcmp_handle* h, const double* q, int64_t n, int32_t* collide
  * sum).  The q-independent half of tcmp_check_body. */
 int tcmp_base_pd(tcmp_handle* h, double* pd, int32_t n);
 
+/* debug: one stage of the device's pair-depth chain on n given (link, pose, obstacle) pairs of
+ * the scene set on the handle, one wave per pair, through the production device function with
+ * the arguments the planner's kernels hand it.  No reference counterpart.
+ * link: moving-link index 0..9; pose: n x 12, the link frame (R row-major, p) as tcmp_fk lays
+ * it out; obstacle: box index, then n_box + mesh index (tcmp_base_pd's order).
+ * stage -> pd (info is 0 unless stated):
+ *   CHAIN       the whole chain (exact_pair); only pd >= 0.04 is meaningful
+ *   BOX32/64    hull-vs-box in fp32 (NaN = "needs fp64") / fp64, on a box obstacle or on a
+ *               mesh's outer box (flag INNER_BOX: its inner box)
+ *   HULL32      fp32 hull-vs-hull on the full hulls, stop = 0.04 - 1e-4 (value, or NaN)
+ *   HULL64      its fp64 restatement (returns early with an upper bound once below 0.04)
+ *   LOD_IN/OUT  fp32 hull-vs-hull on the inner / outer level-of-detail hulls with their
+ *               production stop (0.04 + 1e-4 / 0.04 - 1e-4); value or NaN
+ *   FACET_AXES  the facet trial axes: an upper bound of the depth, or +inf
+ *   SPHERE_CERT the inscribed-sphere certificate: pd 0, info 0 free / 1 collision / 2 undecided
+ * An fp32 hull-vs-hull value below its stop is only an upper bound (early exit).
+ * flag NO_PRUNE (HULL32, HULL64, LOD_IN, LOD_OUT): no Gauss-map cluster is skipped.
+ * Returns -1 when the stage does not apply to a pair (a mesh stage on a box, a LOD stage on a
+ * mesh without LODs, a sphere stage without spheres, INNER_BOX without an inner box) and
+ * while self-collision pairs are on. */
+enum {
+  TCMP_PD_CHAIN = 0, TCMP_PD_BOX32 = 1, TCMP_PD_BOX64 = 2, TCMP_PD_HULL32 = 3, TCMP_PD_HULL64 = 4,
+  TCMP_PD_LOD_IN = 5, TCMP_PD_LOD_OUT = 6, TCMP_PD_FACET_AXES = 7, TCMP_PD_SPHERE_CERT = 8
+};
+enum { TCMP_PD_NO_PRUNE = 1, TCMP_PD_INNER_BOX = 2 };
+int tcmp_debug_pair_pd(tcmp_handle* h, const int32_t* link, const double* pose,
+                       const int32_t* obstacle, int64_t n, int32_t stage, int32_t flags,
+                       double* pd, int32_t* info);
+
+/* debug, host only (no device call): the Gauss-map edge records and cluster cones of n hulls,
+ * exactly as tcmp_set_meshes / tcmp_set_mesh_lods upload them.  No reference counterpart.
+ * records: E x 16 doubles (c = -n1, d = -n2, unit(d x c), edge vector, endpoint, 0), each
+ * hull's rows sorted by arc direction; cones: C x 8 floats (axis, cos and sin of the
+ * half-angle, first and end record row as int bits, 0), room for 128 per hull;
+ * cluster_off: n + 1, hull m's cones are rows [cluster_off[m], cluster_off[m + 1]). */
+int tcmp_gauss_clusters(const tcmp_hulls* H, int32_t n, double* records, float* cones,
+                        int32_t* cluster_off);
+
 /* safe_path_force_aware(extend(from, to), collision, torque) for n edges (rrt_star.py:90-98,
  * utils.py:3068-3077 with the given resolution vector (7, NULL = 0.1 as the planner uses)).
  * n_safe = len(safe prefix), n_steps = len(extend), last = prefix[-1] (valid if n_safe>0). */

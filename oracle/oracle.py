@@ -66,6 +66,15 @@ def lib():
         L.orc_set_meshes.argtypes = [_dp, _ip, _dp, _ip, _ip, _ip, _dp, ctypes.c_int]
         L.orc_mesh_pair_pd.argtypes = [ctypes.c_int, _dp, ctypes.c_int, ctypes.c_int]
         L.orc_mesh_pair_pd.restype = ctypes.c_double
+        L.orc_mesh_pair_pd_pose.argtypes = [ctypes.c_int, _dp, ctypes.c_int, ctypes.c_int]
+        L.orc_mesh_pair_pd_pose.restype = ctypes.c_double
+        L.orc_pair_pd_pose.argtypes = [ctypes.c_int, _dp, _dp, ctypes.c_int]
+        L.orc_pair_pd_pose.restype = ctypes.c_double
+        L.orc_gauss_pairs.argtypes = [_dp, _dp, ctypes.c_int, _dp, _ip, _ip, ctypes.c_int,
+                                      ctypes.c_int, ctypes.c_int,
+                                      ctypes.POINTER(ctypes.c_ubyte), ctypes.POINTER(ctypes.c_long)]
+        L.orc_gauss_pairs.restype = ctypes.c_long
+        L.orc_pair_pd_pose_batch.argtypes = [_ip, _dp, _ip, _dp, ctypes.c_long, ctypes.c_int, _dp]
         L.orc_set_self_collision.argtypes = [ctypes.c_int]
         L.orc_self_pairs.argtypes = [_ip]
         L.orc_self_pair_pd.argtypes = [ctypes.c_int, ctypes.c_int, _dp, ctypes.c_int]
@@ -222,6 +231,51 @@ def mesh_pair_pd(link, q, m, method=0):
     candidate axis), 1 Gauss-map pruned."""
     q = _arr(q, (7,))
     return lib().orc_mesh_pair_pd(int(link), _d(q), int(m), int(method))
+
+
+def mesh_pair_pd_pose(link, fr12, m, method=0):
+    """mesh_pair_pd at a given link frame (12,): R row-major then p, a row of fk_links."""
+    fr = _arr(fr12, (12,))
+    return lib().orc_mesh_pair_pd_pose(int(link), _d(fr), int(m), int(method))
+
+
+def pair_pd_pose(link, fr12, box15, method=0):
+    """pair_pd (methods 0 and 1) at a given link frame (12,): R row-major then p."""
+    fr = _arr(fr12, (12,)); b = _arr(box15, (15,))
+    return lib().orc_pair_pd_pose(int(link), _d(fr), _d(b), int(method))
+
+
+def gauss_pairs(a, b, rec, cluster, hull, n_cluster, n_hull, count=None):
+    """Edge pairs passing the strict fp64 Gregorius test as the device's fp64 pass writes it:
+    a, b (nA, 3) world facet normals of A's edges, rec (nB, 16) Gauss-map records, cluster /
+    hull (nB,) intc ids.  Returns (hit (nA, n_cluster) uint8, count (n_hull,) passing pairs per
+    hull, added to `count` when given)."""
+    a = _arr(a, (-1, 3)); b = _arr(b, (-1, 3)); rec = _arr(rec, (-1, 16))
+    cluster = np.ascontiguousarray(cluster, dtype=np.intc)
+    hull = np.ascontiguousarray(hull, dtype=np.intc)
+    hit = np.zeros((len(a), int(n_cluster)), dtype=np.uint8)
+    if count is None:
+        count = np.zeros(int(n_hull), dtype=np.int_)
+    assert count.dtype == np.int_ and count.flags.c_contiguous and len(count) == n_hull
+    lib().orc_gauss_pairs(_d(a), _d(b), len(a), _d(rec), cluster.ctypes.data_as(_ip),
+                          hull.ctypes.data_as(_ip), len(rec), int(n_cluster), int(n_hull),
+                          hit.ctypes.data_as(ctypes.POINTER(ctypes.c_ubyte)),
+                          count.ctypes.data_as(ctypes.POINTER(ctypes.c_long)))
+    return hit, count
+
+
+def pair_pd_pose_batch(link, fr12, obstacle, method=1, boxes=None):
+    """mesh_pair_pd_pose (boxes None: obstacle = installed mesh index) or pair_pd_pose (obstacle
+    = row of boxes (k, 15)) for n pairs at once, on the library's OpenMP threads."""
+    fr = _arr(fr12, (-1, 12))
+    n = len(fr)
+    link = np.ascontiguousarray(np.broadcast_to(np.asarray(link, dtype=np.intc), (n,)))
+    ob = np.ascontiguousarray(np.broadcast_to(np.asarray(obstacle, dtype=np.intc), (n,)))
+    b = None if boxes is None else _arr(boxes, (-1, 15))
+    out = np.zeros(n)
+    lib().orc_pair_pd_pose_batch(link.ctypes.data_as(_ip), _d(fr), ob.ctypes.data_as(_ip),
+                                 None if b is None else _d(b), n, int(method), _d(out))
+    return out
 
 
 def check_edge(q1, q2, obs, torque_mode, mass, cull=1):

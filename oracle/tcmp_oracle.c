@@ -667,6 +667,15 @@ ORC_API double orc_pair_pd(int link, const double* q, const double* ob, int meth
   return orc_hull_box_pd_local(link, cl, A, ob + 12);
 }
 
+/* The same depths at a given link frame fr (R(9) row-major, p(3): a row of orc_fk_links)
+ * instead of a configuration; methods 0 and 1 of orc_pair_pd. */
+ORC_API double orc_pair_pd_pose(int link, const double* fr, const double* ob, int method) {
+  double cl[3], A[9];
+  box_to_link(fr, ob, cl, A);
+  if (method == 1) return orc_hull_box_pd_gauss(link, cl, A, ob + 12);
+  return orc_hull_box_pd_local(link, cl, A, ob + 12);
+}
+
 /* ------------------------------------------------------------------------------------ */
 /* Collision: moving link convex hull vs convex-mesh obstacle (Bullet GEOM_MESH = convex hull */
 /* of the mesh vertices), penetration >= 0.04.  World-frame hull data set by              */
@@ -858,6 +867,60 @@ ORC_API double orc_hull_mesh_pd_gauss(int link, const double* fr, int m) {
                        g_mesh.e + 4 * g_mesh.eoff[m], g_mesh.eoff[m + 1] - g_mesh.eoff[m]);
 }
 
+/* The strict Gregorius test of one edge of A (facet normals a, b; u = b x a) against a block of
+ * records held by component (c, d, w = unit(d x c)): flag[k] = the arcs intersect. */
+__attribute__((optimize("O3"), target_clones("avx2", "default"))) static void gauss_test_block(
+    const double* soa, size_t nB, size_t k0, int n, const double* a, const double* b,
+    unsigned char* flag) {
+  const double ax = a[0], ay = a[1], az = a[2], bx = b[0], by = b[1], bz = b[2];
+  const double ux = by * az - bz * ay, uy = bz * ax - bx * az, uz = bx * ay - by * ax;
+  const double *cx = soa + k0, *cy = cx + nB, *cz = cy + nB, *dx = cz + nB, *dy = dx + nB,
+               *dz = dy + nB, *wx = dz + nB, *wy = wx + nB, *wz = wy + nB;
+  for (int k = 0; k < n; ++k) {
+    const double cba = cx[k] * ux + cy[k] * uy + cz[k] * uz;
+    const double dba = dx[k] * ux + dy[k] * uy + dz[k] * uz;
+    const double adc = ax * wx[k] + ay * wy[k] + az * wz[k];
+    const double bdc = bx * wx[k] + by * wy[k] + bz * wz[k];
+    flag[k] = (unsigned char)((cba * dba < 0) & (adc * bdc < 0) & (cba * bdc > 0));
+  }
+}
+
+/* Test support for the Gauss-map cluster cones (tests/test_gauss_clusters.py): every (edge of
+ * A, record of B) pair that passes the strict Gregorius test, exactly as the device's fp64 pass
+ * (csrc/tcmp_mesh.h exact_mesh_wave) writes it.  a, b: nA x 3, the world-frame facet normals of
+ * A's edges; rec: nB x 16 Gauss-map records (c, d, unit(d x c), ...); cluster / hull: each
+ * record's cluster (< nC) and hull (< nH).  hit[nA x nC] is set where edge i has a passing
+ * pair in cluster k; count[nH] gains each hull's passing pairs.  Returns their total. */
+ORC_API long orc_gauss_pairs(const double* a, const double* b, int nA, const double* rec,
+                             const int* cluster, const int* hull, int nB, int nC, int nH,
+                             unsigned char* hit, long* count) {
+  long total = 0;
+  memset(hit, 0, (size_t)nA * (size_t)nC);
+  if (nA <= 0 || nB <= 0) return 0;
+  double* soa = malloc(sizeof(double) * 9 * (size_t)nB);
+  for (int k = 0; k < nB; ++k)
+    for (int j = 0; j < 9; ++j) soa[(size_t)j * nB + k] = rec[16 * (size_t)k + j];
+  enum { BLK = 1024 };
+#pragma omp parallel for schedule(static) reduction(+ : total)
+  for (int i = 0; i < nA; ++i) {
+    unsigned char flag[BLK];
+    for (int k0 = 0; k0 < nB; k0 += BLK) {
+      const int kn = nB - k0 < BLK ? nB - k0 : BLK;
+      gauss_test_block(soa, (size_t)nB, (size_t)k0, kn, a + 3 * i, b + 3 * i, flag);
+      for (int k = 0; k < kn; ++k) {
+        if (!flag[k]) continue;
+        hit[(size_t)i * nC + cluster[k0 + k]] = 1;
+#pragma omp atomic
+        count[hull[k0 + k]] += 1;
+        ++total;
+      }
+    }
+  }
+  free(soa);
+  (void)nH;
+  return total;
+}
+
 /* ------------------------------------------------------------------------------------ */
 /* self-collision pairs (get_collision_fn self_collisions=True, utils.py:3165-3191)        */
 /* ------------------------------------------------------------------------------------ */
@@ -961,6 +1024,22 @@ static int orc_mesh_pair_collides(int link, const double* fr, int m, int cull, l
   if (n_exact) ++*n_exact;
   if (cull == 2) return orc_hull_mesh_pd_gauss(link, fr, m) >= ORC_PEN;
   return orc_hull_mesh_pd_brute(link, fr, m) >= ORC_PEN;
+}
+
+/* method 0 brute force, 1 Gauss-map pruned; at a given link frame fr (R(9) row-major, p(3)) */
+ORC_API double orc_mesh_pair_pd_pose(int link, const double* fr, int m, int method) {
+  if (method == 1) return orc_hull_mesh_pd_gauss(link, fr, m);
+  return orc_hull_mesh_pd_brute(link, fr, m);
+}
+
+/* n pairs at once (test fixtures: pose searches evaluate thousands): obstacle m[i] is an
+ * installed mesh, or with box15 != NULL row m[i] of those boxes */
+ORC_API void orc_pair_pd_pose_batch(const int* link, const double* fr, const int* m,
+                                    const double* box15, long n, int method, double* out) {
+#pragma omp parallel for schedule(dynamic, 4)
+  for (long i = 0; i < n; ++i)
+    out[i] = box15 ? orc_pair_pd_pose(link[i], fr + 12 * i, box15 + 15 * (size_t)m[i], method)
+                   : orc_mesh_pair_pd_pose(link[i], fr + 12 * i, m[i], method);
 }
 
 /* method 0 brute force, 1 Gauss-map pruned */

@@ -78,7 +78,9 @@ def test_mesh_and_boxes_vs_oracle(eng):
 
 def test_mesh_pairs_near_threshold(eng):
     """Configurations placed so that single pairs sit near the 0.04 m threshold (the fp32
-    pass defers to fp64 there): flags against the oracle's brute-force depth."""
+    pass defers to fp64 there): flags against the oracle's brute-force depth.  "Near" is
+    +-3 cm here, through FK and the whole check; tests/test_gpu_pair_depth.py places pairs within
+    1e-7 .. 5e-3 m of the threshold and reads every stage's depth."""
     from torque_constrained_motion_planning_amd.scene import ConvexMesh
     from torque_constrained_motion_planning_amd.hull import library_shapes, pack_meshes
     rng = np.random.default_rng(5)

@@ -18,7 +18,7 @@ for line in out.splitlines():
         cur = {"name": name.replace("(anonymous namespace)::", "")}
         rows.append(cur)
         continue
-    for key, pat in (("vgpr", r" VGPRs: (\d+)"), ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"),
+    for key, pat in (("vgpr", r" VGPRs: (\d+)"), ("sgpr", r"TotalSGPRs: (\d+)"), ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"),
                      ("occ", r"Occupancy \[waves/SIMD\]: (\d+)"), ("lds", r"LDS Size \[bytes/block\]: (\d+)"),
                      ("sspill", r"SGPRs Spill: (\d+)"), ("vspill", r"VGPRs Spill: (\d+)")):
         m = re.search(pat, line)
@@ -28,6 +28,6 @@ flt = sys.argv[1] if len(sys.argv) > 1 else ""
 for r in rows:
     if "rocprim" in r["name"] or flt not in r["name"]:
         continue
-    print("vgpr %3s scratch %4s occ %s lds %6s sspill %3s vspill %3s  %s" % (
-        r.get("vgpr"), r.get("scratch"), r.get("occ"), r.get("lds"), r.get("sspill"),
+    print("vgpr %3s sgpr %3s scratch %4s occ %s lds %6s sspill %3s vspill %3s  %s" % (
+        r.get("vgpr"), r.get("sgpr"), r.get("scratch"), r.get("occ"), r.get("lds"), r.get("sspill"),
         r.get("vspill"), r["name"][:90]))

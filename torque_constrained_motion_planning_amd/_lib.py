@@ -38,7 +38,12 @@ EXPORTS = [
     "tcmp_gather_layout", "tcmp_gather_pack", "tcmp_gather_unpack", "tcmp_dist_rccl_ranks",
     "tcmp_shortcut_path", "tcmp_plan_shortcut",
     "tcmp_tier0_tables", "tcmp_tier0_masks",
+    "tcmp_debug_pair_pd", "tcmp_gauss_clusters",
 ]
+# tcmp_debug_pair_pd: stages of the pair-depth chain and its flags (include/tcmp.h)
+(PD_CHAIN, PD_BOX32, PD_BOX64, PD_HULL32, PD_HULL64, PD_LOD_IN, PD_LOD_OUT, PD_FACET_AXES,
+ PD_SPHERE_CERT) = range(9)
+PD_NO_PRUNE, PD_INNER_BOX = 1, 2
 TRAJ_COLS = 22
 REDUCE_SUM, REDUCE_MAX = 0, 1
 
@@ -202,6 +207,11 @@ def load_library(path=LIB_PATH):
             _f32p, _u32p = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_uint32)
             L.tcmp_tier0_tables.argtypes = [_dp, ctypes.c_int32, ctypes.c_int32, _f32p, _u32p, _f32p]
             L.tcmp_tier0_masks.argtypes = [_u32p, ctypes.c_int32, _f32p, _f32p, ctypes.c_int64, _u32p]
+        if hasattr(L, "tcmp_debug_pair_pd"):  # absent from A/B builds of older sources
+            L.tcmp_debug_pair_pd.argtypes = [vp, _i32p, _dp, _i32p, ctypes.c_int64, ctypes.c_int32,
+                                             ctypes.c_int32, _dp, _i32p]
+            L.tcmp_gauss_clusters.argtypes = [ctypes.POINTER(Hulls), ctypes.c_int32, _dp,
+                                              ctypes.POINTER(ctypes.c_float), _i32p]
         _lib = L
         return L
 
@@ -378,6 +388,22 @@ class Engine:
         out = np.zeros(n)
         self._check(self.L.tcmp_base_pd(self.h, _d(out) if n else None, n))
         return out
+
+    def debug_pair_pd(self, link, pose, obstacle, stage, flags=0):
+        """One stage (PD_*) of the pair-depth chain on given pairs (tcmp_debug_pair_pd): link
+        (n,), pose (n, 12) link frames as fk / the oracle's fk_links lay them out, obstacle (n,)
+        box index, then n_box + mesh index.  Returns (pd (n,), info (n,)); raises when the stage
+        does not apply to a pair."""
+        pose = np.ascontiguousarray(np.asarray(pose, dtype=np.float64).reshape(-1, 12))
+        n = len(pose)
+        link = np.ascontiguousarray(np.broadcast_to(np.asarray(link, dtype=np.int32), (n,)))
+        obstacle = np.ascontiguousarray(np.broadcast_to(np.asarray(obstacle, dtype=np.int32), (n,)))
+        pd = np.zeros(n)
+        info = np.zeros(n, dtype=np.int32)
+        self._check(self.L.tcmp_debug_pair_pd(self.h, link.ctypes.data_as(_i32p), _d(pose),
+                                              obstacle.ctypes.data_as(_i32p), n, int(stage),
+                                              int(flags), _d(pd), info.ctypes.data_as(_i32p)))
+        return pd, info
 
     def check_edges(self, q_from, q_to, mode, mass, resolutions=None):
         a = _rows(q_from, "from"); b = _rows(q_to, "to")
@@ -745,6 +771,29 @@ def plan_run_fused(engines, n_samples, batch):
     rc = L.tcmp_plan_run_fused(arr, len(engines), int(n_samples), int(batch))
     if rc != 0:
         raise TcmpError("tcmp error %d: %s" % (rc, L.tcmp_last_error().decode()))
+
+
+def gauss_clusters(hulls):
+    """Host only: the Gauss-map records and cluster cones of a hull.HullSet as the engine
+    uploads them (tcmp_gauss_clusters): records (E, 16) float64 sorted per hull, cones (C, 8)
+    float32 (axis, cos, sin of the half-angle, first / end record row as int bits, 0) and
+    cluster_off (n + 1,)."""
+    L = load_library()
+    i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)  # noqa: E731
+    ip = lambda a: a.ctypes.data_as(_i32p)  # noqa: E731
+    a = (np.ascontiguousarray(hulls.verts, dtype=np.float64), i32(hulls.vert_off),
+         np.ascontiguousarray(hulls.planes, dtype=np.float64), i32(hulls.plane_off),
+         i32(hulls.edges), i32(hulls.edge_off))
+    n = len(a[1]) - 1
+    H = Hulls(_d(a[0]), ip(a[1]), _d(a[2]), ip(a[3]), ip(a[4]), ip(a[5]))
+    rec = np.zeros((int(a[5][-1]), 16))
+    cones = np.zeros((128 * max(n, 1), 8), dtype=np.float32)
+    off = np.zeros(n + 1, dtype=np.int32)
+    rc = L.tcmp_gauss_clusters(ctypes.byref(H), n, _d(rec),
+                               cones.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), ip(off))
+    if rc != 0:
+        raise TcmpError("tcmp error %d: %s" % (rc, L.tcmp_last_error().decode()))
+    return rec, cones[:off[-1]].copy(), off
 
 
 def engine(device=0):

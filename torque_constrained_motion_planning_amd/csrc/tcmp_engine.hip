@@ -1125,6 +1125,119 @@ __global__ __launch_bounds__(256) void k_check_configs(const double* q, long lon
   if (act) collides[i] = c ? 1 : 0;
 }
 
+// One stage of the pair-depth chain (exact_pair and the certificates ahead of it) on given
+// (link, pose, obstacle) pairs, one wave per pair (tcmp_debug_pair_pd): LDS staged as
+// k_check_configs stages it, the pose from the argument instead of FK, then the production
+// device function with the arguments exact_pair / collides_wave hand it.  The host has checked
+// that the stage applies to every pair (indices in range, LODs / spheres / inner box present).
+enum {
+  kDbgChain = 0, kDbgBox32, kDbgBox64, kDbgHull32, kDbgHull64, kDbgLodIn, kDbgLodOut,
+  kDbgFacetAxes, kDbgSphereCert, kDbgStages
+};
+constexpr int kDbgNoPrune = 1, kDbgInnerBox = 2;
+template <bool MESH>
+__global__ __launch_bounds__(256) void k_debug_pair_pd(const int* link, const double* pose,
+                                                       const int* obstacle, int n, int stage,
+                                                       int flags, Scene sc_g, Geo g_g, double* pd,
+                                                       int* info) {
+  extern __shared__ double tcmp_lds[];
+  Scene sc;
+  Geo g;
+  stage_lds<!MESH>(sc_g, g_g, tcmp_lds, sc, g);
+  const int i = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
+  if (i >= n) return;
+  const int lane = lane_id();
+  const int lk = __builtin_amdgcn_readfirstlane(link[i]);
+  const int o = __builtin_amdgcn_readfirstlane(obstacle[i]);
+  Pose PL;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) PL.R[k] = pose[12 * (size_t)i + k];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) PL.p[k] = pose[12 * (size_t)i + 9 + k];
+  // mesh kernels: the pose column of the wave's LDS stash, as phase B leaves it for exact_pair
+  const double* ps = nullptr;
+  if (MESH) {
+    double* st = wave_stash(sc.wq) + 14 * 64;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) st[k * 64 + lane] = PL.R[k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) st[(9 + k) * 64 + lane] = PL.p[k];
+    __asm__ volatile("" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+    ps = st;
+  }
+  auto pose_to_lds = [&]() {
+    double* slot = wave_pose_slot(sc.wq);
+    if (lane == 0) {
+#pragma unroll
+      for (int k = 0; k < 9; ++k) slot[k] = PL.R[k];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) slot[9 + k] = PL.p[k];
+    }
+    __builtin_amdgcn_wave_barrier();
+    return (const double*)slot;
+  };
+  const double* ob = sc.obs + 16 * o;
+  const int mi = MESH ? obs_mesh(ob) : -1;
+  constexpr float P = (float)kPen;
+  double out = __builtin_nan("");
+  int inf = 0;
+  if (stage == kDbgChain) {
+    out = exact_pair<MESH>(lk, PL, ps, ob, sc, g);
+  } else if (stage == kDbgBox32 || stage == kDbgBox64) {
+    // a box obstacle, or a mesh's outer box (its obstacle record) / inner box (Scene::mib)
+    const double* bx = (MESH && mi >= 0 && (flags & kDbgInnerBox)) ? sc.mib + 16 * mi : ob;
+    if (stage == kDbgBox32) out = (double)exact_pd_wave32(lk, PL, bx, g, mi < 0);
+    else out = exact_pd_wave(lk, pose_to_lds(), bx, g.verts, g.planes, g.edges);
+  } else if constexpr (MESH) {
+    const int* rg = sc.mrange + kMrange * mi;
+    float R[9], p[3];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) R[k] = (float)PL.R[k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) p[k] = (float)PL.p[k];
+    const bool prune = !(flags & kDbgNoPrune);
+    if (stage == kDbgHull32) {
+      const HullA32 A{g.verts32, g.planes32, g.eidx, sc.geo_ev, tcmp_geo_vert_off[lk],
+                      tcmp_geo_vert_off[lk + 1], tcmp_geo_plane_off[lk], tcmp_geo_plane_off[lk + 1],
+                      tcmp_geo_edge_off[lk], tcmp_geo_edge_off[lk + 1]};
+      const HullB32 B{sc.mv32, sc.mp32, sc.me32, rg[0], rg[1], rg[2], rg[3], rg[4], rg[5], sc.mcl,
+                      rg[20], rg[21]};
+      out = (double)(prune ? hull_hull_wave32<true, true>(A, B, R, p, P - kExactGuard)
+                           : hull_hull_wave32<true, false>(A, B, R, p, P - kExactGuard));
+    } else if (stage == kDbgHull64) {
+      const double* sl = pose_to_lds();
+      out = prune ? exact_mesh_wave<true>(lk, sl, mi, sc.mrange, sc.mp64, sc.mv64, sc.me64, sc.mcl,
+                                          g.verts, g.planes, g.edges)
+                  : exact_mesh_wave<false>(lk, sl, mi, sc.mrange, sc.mp64, sc.mv64, sc.me64, sc.mcl,
+                                           g.verts, g.planes, g.edges);
+    } else if (stage == kDbgLodIn || stage == kDbgLodOut) {
+      // inner LODs against kPen + guard ("collision" above), outer against kPen - guard ("free")
+      const int x = stage == kDbgLodOut ? 1 : 0;
+      const int* vo = x ? tcmp_lod_out_vert_off : tcmp_lod_in_vert_off;
+      const int* po = x ? tcmp_lod_out_plane_off : tcmp_lod_in_plane_off;
+      const int* eo = x ? tcmp_lod_out_edge_off : tcmp_lod_in_edge_off;
+      const int* r = rg + 6 + 6 * x;
+      const HullA32 A{sc.lodv3[x], sc.lodpl[x], sc.lodei[x], sc.lodev[x], vo[lk], vo[lk + 1], po[lk],
+                      po[lk + 1], eo[lk], eo[lk + 1]};
+      const HullB32 B{sc.lv32[x], sc.lp32[x], sc.le32[x], r[0], r[1], r[2], r[3], r[4], r[5],
+                      sc.lcl[x], rg[22 + 2 * x], rg[23 + 2 * x]};
+      const float stop = x ? P - kExactGuard : P + kExactGuard;
+      out = (double)(prune ? hull_hull_wave32<false, true>(A, B, R, p, stop)
+                           : hull_hull_wave32<false, false>(A, B, R, p, stop));
+    } else if (stage == kDbgFacetAxes) {
+      out = (double)facet_axes_wave(lk, R, p, mi, rg, sc, g);
+    } else if (stage == kDbgSphereCert) {
+      inf = sphere_cert(lk, R, p, mi, sc, g);
+      out = 0.0;
+    }
+  }
+  if (lane == 0) {
+    pd[i] = out;
+    info[i] = inf;
+  }
+}
+
 template <int MODE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE == 3 ? 1 : 2))) void k_torque(const double* q, const double* qd, const double* qdd, long long n,
                          double mass, int* ok) {
@@ -1944,6 +2057,7 @@ int tcmp_create(int device, tcmp_handle** out) {
                           (const void*)k_edges<false, 2>, (const void*)k_edges<true, 2>,
                           (const void*)k_edges<false, 4>, (const void*)k_edges<true, 4>,
                           (const void*)k_check_configs<false>, (const void*)k_check_configs<true>,
+                          (const void*)k_debug_pair_pd<false>, (const void*)k_debug_pair_pd<true>,
                           (const void*)k_rewire_apply<false>, (const void*)k_rewire_apply<true>})
       HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
     if (int rc2 = fleet_lds_limits()) { delete h; return rc2; }
@@ -2804,6 +2918,81 @@ int tcmp_base_pd(tcmp_handle* h, double* pd, int32_t n) {
   HIPCHK(hipMemcpyAsync(pd, h->base_pd.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost,
                         h->stream));
   if (int rc_s = sync_stream(h)) return rc_s;
+  return 0;
+}
+
+int tcmp_debug_pair_pd(tcmp_handle* h, const int32_t* link, const double* pose,
+                       const int32_t* obstacle, int64_t n, int32_t stage, int32_t flags,
+                       double* pd, int32_t* info) {
+  TCMP_ENTER(h);
+  if (n < 0 || n > (1 << 22) || (n > 0 && (!link || !pose || !obstacle || !pd || !info)))
+    return fail(-1, "bad arguments");
+  if (stage < 0 || stage >= kDbgStages) return fail(-1, "unknown stage");
+  if (flags & ~(kDbgNoPrune | kDbgInnerBox)) return fail(-1, "unknown flag");
+  if (h->self_coll) return fail(-1, "pair probes take no self-collision pairs");
+  if (n == 0) return 0;
+  const bool mesh_stage = stage >= kDbgHull32;
+  const bool prunes = stage == kDbgHull32 || stage == kDbgHull64 || stage == kDbgLodIn ||
+                      stage == kDbgLodOut;
+  if ((flags & kDbgNoPrune) && !prunes) return fail(-1, "NO_PRUNE: hull-vs-hull stages only");
+  if ((flags & kDbgInnerBox) && stage != kDbgBox32 && stage != kDbgBox64)
+    return fail(-1, "INNER_BOX: box stages only");
+  for (int64_t i = 0; i < n; ++i) {
+    if (link[i] < 0 || link[i] >= TCMP_NLINKS) return fail(-1, "link index out of range");
+    if (obstacle[i] < 0 || obstacle[i] >= h->n_box + h->n_mesh)
+      return fail(-1, "obstacle index out of range");
+    for (int k = 0; k < 12; ++k)
+      if (!std::isfinite(pose[12 * i + k])) return fail(-1, "pose is not finite");
+    const int m = obstacle[i] - h->n_box;
+    if (m < 0) {
+      if (mesh_stage) return fail(-1, "a mesh stage on a box obstacle");
+      if (flags & kDbgInnerBox) return fail(-1, "a box obstacle has no inner box");
+      continue;
+    }
+    const int* rg = h->mrange_h.data() + kMrange * m;
+    if ((stage == kDbgLodIn || stage == kDbgLodOut) && !rg[18])
+      return fail(-1, "the mesh has no level-of-detail hulls");
+    if ((stage == kDbgFacetAxes || stage == kDbgSphereCert) && !rg[19])
+      return fail(-1, "the mesh has no inscribed spheres");
+    if ((flags & kDbgInnerBox) && !(h->mesh_box[18 * (size_t)m + 15] > 0.0))
+      return fail(-1, "the mesh has no inner box");
+  }
+  int rc = h->s0.ensure((size_t)n * 12);
+  rc = rc ? rc : h->s1.ensure((size_t)n);
+  rc = rc ? rc : h->i0.ensure((size_t)n);
+  rc = rc ? rc : h->i1.ensure((size_t)n);
+  rc = rc ? rc : h->i2.ensure((size_t)n);
+  if (rc) return rc;
+  HIPCHK(hipMemcpyAsync(h->s0.p, pose, (size_t)n * 12 * sizeof(double), hipMemcpyHostToDevice,
+                        h->stream));
+  HIPCHK(hipMemcpyAsync(h->i0.p, link, (size_t)n * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->i1.p, obstacle, (size_t)n * sizeof(int), hipMemcpyHostToDevice,
+                        h->stream));
+  hipLaunchKernelGGL(h->mesh_kernels() ? k_debug_pair_pd<true> : k_debug_pair_pd<false>,
+                     dim3(grid_for(n, 4)), dim3(256), lds_bytes(h), h->stream, h->i0.p, h->s0.p,
+                     h->i1.p, (int)n, (int)stage, (int)flags, h->scene(), h->geo(), h->s1.p,
+                     h->i2.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(pd, h->s1.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(info, h->i2.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  if (int rc_s = sync_stream(h)) return rc_s;
+  return 0;
+}
+
+int tcmp_gauss_clusters(const tcmp_hulls* H, int32_t n, double* records, float* cones,
+                        int32_t* cluster_off) {
+  if (n < 0 || (n > 0 && (!records || !cones || !cluster_off))) return fail(-1, "bad arguments");
+  if (n == 0) return 0;
+  if (int rc = check_hulls(H, n, "gauss")) return rc;
+  edge_records(H->verts, H->vert_off, H->planes, H->plane_off, H->edges, H->edge_off, n, records);
+  std::vector<float> cl;
+  cluster_off[0] = 0;
+  for (int m = 0; m < n; ++m) {
+    int c0, c1;
+    gauss_clusters(records, H->edge_off[m], H->edge_off[m + 1], cl, &c0, &c1);
+    cluster_off[m + 1] = c1;
+  }
+  memcpy(cones, cl.data(), cl.size() * sizeof(float));
   return 0;
 }
 

@@ -153,7 +153,9 @@ __device__ __forceinline__ float facets32(const HullA32& A, const HullB32& B, co
 // fp32 penetration depth of hull A (pose R, p) against hull B, wave-cooperative.  Returns as
 // soon as a stage's minimum falls below `stop` (then the value is only an upper bound below
 // `stop`), NaN when an edge axis is too degenerate for fp32 (see the header comment).
-template <bool STAT>
+// PRUNE = false (tcmp_debug_pair_pd only): every edge of A takes the knife-edge branch, so
+// every cluster is a candidate -- the unpruned minimum the pruned one must equal.
+template <bool STAT, bool PRUNE = true>
 __device__ __forceinline__ float hull_hull_wave32(const HullA32 A, const HullB32 B,
                                                   const float R[9], const float p[3], float stop) {
   const int lane = lane_id();
@@ -220,7 +222,7 @@ __device__ __forceinline__ float hull_hull_wave32(const HullA32 A, const HullB32
         // the arc's cone in A's frame, its axis rotated into the world
         const float sx = na.x + nb.x, sy = na.y + nb.y, sz = na.z + nb.z;
         const float s2 = sx * sx + sy * sy + sz * sz;
-        if (!(s2 > 1e-6f)) {
+        if (!PRUNE || !(s2 > 1e-6f)) {
           // a knife edge: no cone, every cluster
 #pragma unroll
           for (int w = 0; w < kClWords; ++w) {
@@ -367,7 +369,9 @@ __device__ __forceinline__ float hull_hull_wave32(const HullA32 A, const HullB32
 // pose: R[9], p[3] in the wave's LDS pose slot; pointers one by one (no argument in scratch)
 // The edge pairs are pruned by the mesh's Gauss-map clusters exactly as in hull_hull_wave32
 // (a cluster whose cone cannot meet the lane's arc holds no intersecting arc; the cones are
-// conservative by kConeSlack), so the minimum is the unpruned one.
+// conservative by kConeSlack), so the minimum is the unpruned one.  PRUNE = false
+// (tcmp_debug_pair_pd only): every edge is treated as a knife edge, no cluster is skipped.
+template <bool PRUNE = true>
 __device__ __noinline__ double exact_mesh_wave(int link, const double* pose, int m,
                                                const int* __restrict__ mrange,
                                                const double4* __restrict__ mp64,
@@ -438,7 +442,7 @@ __device__ __noinline__ double exact_mesh_wave(int link, const double* pose, int
     // the lane's arc a -> b in its cone (unit(a + b), half the a-b angle), fp32
     const double sx = ax + bx, sy = ay + by, sz = az + bz;
     const double s2 = sx * sx + sy * sy + sz * sz;
-    const bool knife = !(s2 > 1e-6);  // antipodal normals: no cone, every cluster
+    const bool knife = !PRUNE || !(s2 > 1e-6);  // antipodal normals: no cone, every cluster
     const float is = knife ? 0.f : (float)(1.0 / sqrt(s2));
     const float qx = (float)sx * is, qy = (float)sy * is, qz = (float)sz * is;
     const double cab = ax * bx + ay * by + az * bz;
