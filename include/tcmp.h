@@ -192,6 +192,13 @@ int tcmp_debug_pair_pd(tcmp_handle* h, const int32_t* link, const double* pose,
                        const int32_t* obstacle, int64_t n, int32_t stage, int32_t flags,
                        double* pd, int32_t* info);
 
+/* debug: the device's fp32 wave reductions (the helpers of the exact tests and of the scan) on
+ * n given waves, one wave per row, one launch; no scene or plan involved.  No reference
+ * counterpart.  values: n x 64 x 6 floats (wave, lane, column), none NaN.  out: n x 9 --
+ * the six results of the multi-value helper (minima of columns 0..2, maxima of columns 3..5),
+ * then the single-value minimum, maximum and broadcast minimum of column 0. */
+int tcmp_debug_wave_reduce(tcmp_handle* h, const float* values, int64_t n, float* out);
+
 /* debug, host only (no device call): the Gauss-map edge records and cluster cones of n hulls,
  * exactly as tcmp_set_meshes / tcmp_set_mesh_lods upload them.  No reference counterpart.
  * records: E x 16 doubles (c = -n1, d = -n2, unit(d x c), edge vector, endpoint, 0), each

@@ -38,7 +38,7 @@ EXPORTS = [
     "tcmp_gather_layout", "tcmp_gather_pack", "tcmp_gather_unpack", "tcmp_dist_rccl_ranks",
     "tcmp_shortcut_path", "tcmp_plan_shortcut",
     "tcmp_tier0_tables", "tcmp_tier0_masks",
-    "tcmp_debug_pair_pd", "tcmp_gauss_clusters",
+    "tcmp_debug_pair_pd", "tcmp_gauss_clusters", "tcmp_debug_wave_reduce",
 ]
 # tcmp_debug_pair_pd: stages of the pair-depth chain and its flags (include/tcmp.h)
 (PD_CHAIN, PD_BOX32, PD_BOX64, PD_HULL32, PD_HULL64, PD_LOD_IN, PD_LOD_OUT, PD_FACET_AXES,
@@ -212,6 +212,9 @@ def load_library(path=LIB_PATH):
                                              ctypes.c_int32, _dp, _i32p]
             L.tcmp_gauss_clusters.argtypes = [ctypes.POINTER(Hulls), ctypes.c_int32, _dp,
                                               ctypes.POINTER(ctypes.c_float), _i32p]
+        if hasattr(L, "tcmp_debug_wave_reduce"):  # absent from A/B builds of older sources
+            _f32p = ctypes.POINTER(ctypes.c_float)
+            L.tcmp_debug_wave_reduce.argtypes = [vp, _f32p, ctypes.c_int64, _f32p]
         _lib = L
         return L
 
@@ -404,6 +407,21 @@ class Engine:
                                               obstacle.ctypes.data_as(_i32p), n, int(stage),
                                               int(flags), _d(pd), info.ctypes.data_as(_i32p)))
         return pd, info
+
+    def debug_wave_reduce(self, values):
+        """The device's fp32 wave reductions on values (n, 64, 6) -- wave, lane, column -- none
+        NaN (tcmp_debug_wave_reduce).  Returns (n, 9) float32: the multi-value helper's minima of
+        columns 0..2 and maxima of columns 3..5, then wave_minf, wave_maxf, wave_minf_bc of
+        column 0."""
+        v = np.ascontiguousarray(np.asarray(values, dtype=np.float32))
+        if v.ndim != 3 or v.shape[1:] != (64, 6):
+            raise ValueError("values must be (n, 64, 6)")
+        n = len(v)
+        out = np.zeros((n, 9), dtype=np.float32)
+        f32p = ctypes.POINTER(ctypes.c_float)
+        self._check(self.L.tcmp_debug_wave_reduce(self.h, v.ctypes.data_as(f32p), n,
+                                                  out.ctypes.data_as(f32p)))
+        return out
 
     def check_edges(self, q_from, q_to, mode, mass, resolutions=None):
         a = _rows(q_from, "from"); b = _rows(q_to, "to")

@@ -661,7 +661,14 @@ __device__ __noinline__ double exact_pd_wave(int link, const double* pose,
   return fmin(pd, wave_min(loc));
 }
 
-__device__ __forceinline__ float wave_minf(float x) {
+// fp32 wave reductions, two forms.
+// The float chains (wave_minf_fp / wave_maxf_fp): fminf / fmaxf on a value that comes out of a
+// DPP move cost three instructions a step (the move, a NaN-quieting canonicalisation, the min)
+// and a further move ahead of each row_bcast step.  The mesh kernels (MESH = true: the
+// hull-vs-hull chain of tcmp_mesh.h, facet_axes_wave, and exact_pd_wave32<false> on a mesh's
+// outer / inner box) keep them: with the key form k_fl_edges_mesh ran 0.85 % longer on C5
+// (DESIGN.md section 7).
+__device__ __forceinline__ float wave_minf_fp(float x) {
   x = fminf(x, dpp_f<0xB1>(x));
   x = fminf(x, dpp_f<0x4E>(x));
   x = fminf(x, dpp_f<0x124>(x));
@@ -670,16 +677,7 @@ __device__ __forceinline__ float wave_minf(float x) {
   x = fminf(x, bc31_f(x));
   return readlane_f(x, 63);
 }
-__device__ __forceinline__ float wave_minf_bc(float x) {
-  x = fminf(x, dpp_f<0xB1>(x));
-  x = fminf(x, dpp_f<0x4E>(x));
-  x = fminf(x, dpp_f<0x124>(x));
-  x = fminf(x, dpp_f<0x128>(x));
-  x = fminf(x, bc15_f(x));
-  x = fminf(x, bc31_f(x));
-  return readlane_f(x, 63);
-}
-__device__ __forceinline__ float wave_maxf(float x) {
+__device__ __forceinline__ float wave_maxf_fp(float x) {
   x = fmaxf(x, dpp_f<0xB1>(x));
   x = fmaxf(x, dpp_f<0x4E>(x));
   x = fmaxf(x, dpp_f<0x124>(x));
@@ -687,6 +685,92 @@ __device__ __forceinline__ float wave_maxf(float x) {
   x = fmaxf(x, bc15_f(x));
   x = fmaxf(x, bc31_f(x));
   return readlane_f(x, 63);
+}
+// The key form (wave_minf, wave_maxf, wave_minf_bc, wave_minmaxf, wave_minmax3): the same six
+// DPP steps on order-preserving integer keys.  The integer min / max take the DPP control
+// themselves, one instruction a step.  f32_key maps a float's bits to a signed int whose order
+// is the float order for every non-NaN value, infinities included (negative floats: the
+// magnitude bits inverted); it is its own inverse, so the result is decoded from lane 63's key
+// with scalar instructions.  The two row_bcast steps carry the operation's identity as `old`,
+// so the rows outside the row mask keep their value.  Callers: exact_pd_wave32<true> (the box
+// kernels' exact test), refresh() of k_nearest_wave32, the cell-box kernels of tcmp_nn.h.
+// Contract:
+//  - No NaN input (a NaN's key sorts past the infinities, the result would be arbitrary).
+//    exact_pd_wave32 reduces running fminf / fmaxf values that started from +-INFINITY over
+//    sums of products of finite coordinates: fminf / fmaxf drop a NaN operand, so a lane holds
+//    the identity or a finite value.  refresh() passes __double2float_ru(b1), b1 a squared
+//    distance or +inf; the cell-box kernels pass stored finite bounds or the identity.
+//  - The result is one of the inputs: the value the float chains return.
+//  - Zeros: the keys order -0 below +0, the float chains treat them as equal and keep either,
+//    so with both in the input the zero's sign may differ from the chains'.  No caller can
+//    tell: exact_pd_wave32's minima and maxima enter sums and comparisons with
+//    kPen +- kExactGuard, refresh() takes the square root and squares it again, and a cell
+//    box's bound of either zero bounds the same cells.
+// Wave-uniform.  Call with every lane of the wave active.
+__device__ __forceinline__ int f32_key(float x) {
+  // shifts, not `& 0x7fffffff`: the mask form compiles to two instructions but holds the
+  // constant in an SGPR, which costs the kernels at the register cap VGPR spills
+  // (k_fl_edges<false>: two more); this form is three instructions and no register
+  const int i = __float_as_int(x);
+  return i ^ (int)((unsigned)(i >> 31) >> 1);
+}
+__device__ __forceinline__ float key_f32(int k) {
+  return __int_as_float(k ^ (int)((unsigned)(k >> 31) >> 1));
+}
+// step S (0..5) of the reduction of a key: MX ? max : min
+template <bool MX, int S>
+__device__ __forceinline__ int key_step(int k) {
+  constexpr int kId = MX ? INT_MIN : INT_MAX;
+  const int o = S == 0   ? dpp_i<0xB1>(k)
+                : S == 1 ? dpp_i<0x4E>(k)
+                : S == 2 ? dpp_i<0x124>(k)
+                : S == 3 ? dpp_i<0x128>(k)
+                : S == 4 ? __builtin_amdgcn_update_dpp(kId, k, 0x142, 0xA, 0xF, false)
+                         : __builtin_amdgcn_update_dpp(kId, k, 0x143, 0xC, 0xF, false);
+  return MX ? max(k, o) : min(k, o);
+}
+template <bool MX>
+__device__ __forceinline__ float wave_reduce_f32(float x) {
+  int k = f32_key(x);
+  k = key_step<MX, 0>(k);
+  k = key_step<MX, 1>(k);
+  k = key_step<MX, 2>(k);
+  k = key_step<MX, 3>(k);
+  k = key_step<MX, 4>(k);
+  k = key_step<MX, 5>(k);
+  return key_f32(__builtin_amdgcn_readlane(k, 63));
+}
+__device__ __forceinline__ float wave_minf(float x) { return wave_reduce_f32<false>(x); }
+__device__ __forceinline__ float wave_minf_bc(float x) { return wave_reduce_f32<false>(x); }
+__device__ __forceinline__ float wave_maxf(float x) { return wave_reduce_f32<true>(x); }
+// NMN minima and NMX maxima at once, each replaced by its wave_minf / wave_maxf: the chains
+// advance together, NMN + NMX independent instructions a step, so a step's DPP read never
+// waits on the instruction before it and the depth is six steps whatever the count.
+template <int NMN, int NMX>
+__device__ __forceinline__ void wave_minmaxf(float* mn, float* mx) {
+  int a[NMN > 0 ? NMN : 1], b[NMX > 0 ? NMX : 1];
+#pragma unroll
+  for (int j = 0; j < NMN; ++j) a[j] = f32_key(mn[j]);
+#pragma unroll
+  for (int j = 0; j < NMX; ++j) b[j] = f32_key(mx[j]);
+#define TCMP_KEY_STEP(S)                                                           \
+  _Pragma("unroll") for (int j = 0; j < NMN; ++j) a[j] = key_step<false, S>(a[j]); \
+  _Pragma("unroll") for (int j = 0; j < NMX; ++j) b[j] = key_step<true, S>(b[j]);
+  TCMP_KEY_STEP(0) TCMP_KEY_STEP(1) TCMP_KEY_STEP(2) TCMP_KEY_STEP(3) TCMP_KEY_STEP(4)
+  TCMP_KEY_STEP(5)
+#undef TCMP_KEY_STEP
+#pragma unroll
+  for (int j = 0; j < NMN; ++j) mn[j] = key_f32(__builtin_amdgcn_readlane(a[j], 63));
+#pragma unroll
+  for (int j = 0; j < NMX; ++j) mx[j] = key_f32(__builtin_amdgcn_readlane(b[j], 63));
+}
+// the box-face stage of exact_pd_wave32: three minima and three maxima
+__device__ __forceinline__ void wave_minmax3(float& mn0, float& mn1, float& mn2, float& mx0,
+                                             float& mx1, float& mx2) {
+  float mn[3] = {mn0, mn1, mn2}, mx[3] = {mx0, mx1, mx2};
+  wave_minmaxf<3, 3>(mn, mx);
+  mn0 = mn[0]; mn1 = mn[1]; mn2 = mn[2];
+  mx0 = mx[0]; mx1 = mx[1]; mx2 = mx[2];
 }
 
 // fp32 first pass of exact_pd_wave on the LDS geometry.  Same candidate axes and the same
@@ -721,9 +805,12 @@ __device__ unsigned long long g_exact_stats[32];  // [4..7]: mesh pairs (exact_p
                                                   // [8..13]: hull_hull_wave32 exits,
                                                   // [16..20]: exact_pair mesh-stage clocks
 #endif
+// KEYS: the wave reductions in the key form (the box kernels), else the float chains
+template <bool KEYS>
 __device__ __forceinline__ float exact_pd_wave32(int link, const Pose pose,
                                               const double* __restrict__ ob, const Geo g,
                                               bool box_pair = false) {
+  auto wminf = [](float x) { return KEYS ? wave_minf(x) : wave_minf_fp(x); };
   const int lane = lane_id();
 #ifdef TCMP_PROF_EXACT
   // box pairs: stage clocks in g_exact_stats[16..19] (box faces, -, facets, edges) -- slots
@@ -761,8 +848,12 @@ __device__ __forceinline__ float exact_pd_wave32(int link, const Pose pose,
     mn1 = fminf(mn1, d1); mx1 = fmaxf(mx1, d1);
     mn2 = fminf(mn2, d2); mx2 = fmaxf(mx2, d2);
   }
-  mn0 = wave_minf(mn0); mn1 = wave_minf(mn1); mn2 = wave_minf(mn2);
-  mx0 = wave_maxf(mx0); mx1 = wave_maxf(mx1); mx2 = wave_maxf(mx2);
+  if (KEYS) {
+    wave_minmax3(mn0, mn1, mn2, mx0, mx1, mx2);
+  } else {
+    mn0 = wave_minf_fp(mn0); mn1 = wave_minf_fp(mn1); mn2 = wave_minf_fp(mn2);
+    mx0 = wave_maxf_fp(mx0); mx1 = wave_maxf_fp(mx1); mx2 = wave_maxf_fp(mx2);
+  }
   float pd;
   {
     const float pc0 = A[0] * cl[0] + A[3] * cl[1] + A[6] * cl[2];
@@ -791,7 +882,7 @@ __device__ __forceinline__ float exact_pd_wave32(int link, const Pose pose,
   }
   // facet axes are exact overlaps: one below kPen - guard already proves "free"
   {
-    const float lf = fminf(pd, wave_minf(loc));
+    const float lf = fminf(pd, wminf(loc));
     TCMP_BOX_CLK(2);
     if (lf < P - kExactGuard) {
 #ifdef TCMP_PROF_EXACT
@@ -874,7 +965,7 @@ __device__ __forceinline__ float exact_pd_wave32(int link, const Pose pose,
     }
     // early "free" once a trustworthy axis is below kPen - guard (no degenerate axis so far)
     if (w0 + 64 < total && !__ballot(deg)) {
-      const float lf = fminf(pd, wave_minf(loc));
+      const float lf = fminf(pd, wminf(loc));
       if (lf < P - kExactGuard) {
 #ifdef TCMP_PROF_EXACT
         if (lane == 0) atomicAdd(&g_exact_stats[2], 1ull);
@@ -888,7 +979,7 @@ __device__ __forceinline__ float exact_pd_wave32(int link, const Pose pose,
   if (lane == 0) atomicAdd(&g_exact_stats[__ballot(deg) ? 3 : 2], 1ull);
 #endif
   if (__ballot(deg)) return __builtin_nanf("");
-  const float full = fminf(pd, wave_minf(loc));
+  const float full = fminf(pd, wminf(loc));
 #ifdef TCMP_PROF_EXACT
   // box pairs through the whole edge pass: collision / free
   if (lane == 0 && box_pair) atomicAdd(&g_exact_stats[full >= P ? 28 : 29], 1ull);
@@ -928,7 +1019,7 @@ __device__ __forceinline__ float facet_axes_wave(int link, const float R[9], con
     if (ov > best) { best = ov; bx = ex; by = ey; bz = ez; }
   }
   {
-    const float m = wave_maxf(best);
+    const float m = wave_maxf_fp(best);
     const int L = __builtin_ctzll(__ballot(best == m));
     bx = __shfl(bx, L); by = __shfl(by, L); bz = __shfl(bz, L);
     const float l2 = bx * bx + by * by + bz * bz;
@@ -954,7 +1045,7 @@ __device__ __forceinline__ float facet_axes_wave(int link, const float R[9], con
       const float v = n.x * bx + n.y * by + n.z * bz;
       if (v > sl) { sl = v; fl = f; }
     }
-    const float mm = wave_maxf(sm), ml = wave_maxf(sl);
+    const float mm = wave_maxf_fp(sm), ml = wave_maxf_fp(sl);
     fm = __builtin_amdgcn_readfirstlane(__shfl(fm, __builtin_ctzll(__ballot(sm == mm))));
     fl = __builtin_amdgcn_readfirstlane(__shfl(fl, __builtin_ctzll(__ballot(sl == ml))));
   }
@@ -975,8 +1066,8 @@ __device__ __forceinline__ float facet_axes_wave(int link, const float R[9], con
     const float4 x = sc.mv32[w];
     gm = fminf(gm, x.x * wx + x.y * wy + x.z * wz);
   }
-  h = wave_maxf(h);
-  gm = wave_minf(gm);
+  h = wave_maxf_fp(h);
+  gm = wave_minf_fp(gm);
   const float o1 = h - (p[0] * N.x + p[1] * N.y + p[2] * N.z) + N.w;
   const float o2 = F.w + (p[0] * wx + p[1] * wy + p[2] * wz) - gm;
   return fminf(o1, o2);
@@ -1019,7 +1110,7 @@ __device__ __forceinline__ double exact_pair(int link, const Pose PL0, const dou
     return (const double*)slot;
   };
   if (!MESH || mi < 0) {
-    const float pd32 = exact_pd_wave32(link, pose(), ob, g, true);
+    const float pd32 = exact_pd_wave32<!MESH>(link, pose(), ob, g, true);
     if (pd32 == pd32 && fabsf(pd32 - (float)kPen) > kExactGuard) return (double)pd32;
     return exact_pd_wave(link, pose_to_lds(), ob, g.verts, g.planes, g.edges);
   }
@@ -1099,7 +1190,7 @@ __device__ __forceinline__ double exact_pair(int link, const Pose PL0, const dou
   // the outer LOD C5 edges took 10 % less time, without the outer and inner boxes 1 % less
   // (same-box A/Bs, profiles/r9g_ab_c5_chain, r9j_ab_c5_boxes).
   if (!inner_first) {
-    const float po = exact_pd_wave32(link, pose(), ob, g);
+    const float po = exact_pd_wave32<!MESH>(link, pose(), ob, g);
     TCMP_MESH_CLK(0);
     if (po == po && po < P - kExactGuard) { TCMP_MESH_STAT(4); TCMP_FA_REC(po); return (double)po; }
   }
@@ -1122,7 +1213,7 @@ __device__ __forceinline__ double exact_pair(int link, const Pose PL0, const dou
     // the mesh's inner box ("collision" above kPen + guard): meshes without LODs
     const double* ib = sc.mib + 16 * mi;
     if (ib[12] > 0.0) {
-      const float pi = exact_pd_wave32(link, pose(), ib, g);
+      const float pi = exact_pd_wave32<!MESH>(link, pose(), ib, g);
       if (pi == pi && pi > P + kExactGuard) { TCMP_MESH_STAT(6); TCMP_FA_REC(pi); return (double)pi; }
     }
   }

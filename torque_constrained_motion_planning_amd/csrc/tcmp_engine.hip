@@ -703,10 +703,15 @@ __device__ __forceinline__ void rewire_apply_block(const PlanParams* __restrict_
   extern __shared__ double tcmp_lds[];
   Scene sc;
   Geo g;
-  stage_lds<!MESH>(sc_g, g_g, tcmp_lds, sc, g);
   const long long R = st->rw_count, T = st->snap;
+  // a block without a candidate leaves before it stages the scene and the hulls into LDS (the
+  // staging has a barrier, so both returns are block-uniform): past the flagged nodes, or
+  // none of its flagged nodes has a neighbour
+  if ((long long)blk * blockDim.x >= R) return;
   const long long t = (long long)blk * blockDim.x + threadIdx.x;
   const bool act = t < R && ncount[t] > 0;
+  if (!__syncthreads_or(act)) return;
+  stage_lds<!MESH>(sc_g, g_g, tcmp_lds, sc, g);
   if (__ballot(act) == 0) return;  // wave-uniform
   const long long me = act ? rwlist[t] : 0;
   double qn[7];
@@ -1187,7 +1192,7 @@ __global__ __launch_bounds__(256) void k_debug_pair_pd(const int* link, const do
   } else if (stage == kDbgBox32 || stage == kDbgBox64) {
     // a box obstacle, or a mesh's outer box (its obstacle record) / inner box (Scene::mib)
     const double* bx = (MESH && mi >= 0 && (flags & kDbgInnerBox)) ? sc.mib + 16 * mi : ob;
-    if (stage == kDbgBox32) out = (double)exact_pd_wave32(lk, PL, bx, g, mi < 0);
+    if (stage == kDbgBox32) out = (double)exact_pd_wave32<!MESH>(lk, PL, bx, g, mi < 0);
     else out = exact_pd_wave(lk, pose_to_lds(), bx, g.verts, g.planes, g.edges);
   } else if constexpr (MESH) {
     const int* rg = sc.mrange + kMrange * mi;
@@ -1235,6 +1240,30 @@ __global__ __launch_bounds__(256) void k_debug_pair_pd(const int* link, const do
   if (lane == 0) {
     pd[i] = out;
     info[i] = inf;
+  }
+}
+
+// The fp32 wave reductions on given values, one wave per row of 64 lanes x 6 floats
+// (tcmp_debug_wave_reduce).  out [n][9]: wave_minmax3 with columns 0..2 as its minima and
+// columns 3..5 as its maxima, then wave_minf, wave_maxf and wave_minf_bc of column 0.
+__global__ __launch_bounds__(256) void k_debug_wave_reduce(const float* in, int n, float* out) {
+  const int w = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
+  if (w >= n) return;  // wave-uniform
+  const int lane = lane_id();
+  const float* r = in + ((size_t)w * 64 + lane) * 6;
+  float v[6];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) v[k] = r[k];
+  const float x = v[0];
+  wave_minmax3(v[0], v[1], v[2], v[3], v[4], v[5]);
+  const float mn = wave_minf(x), mx = wave_maxf(x), bc = wave_minf_bc(x);
+  if (lane == 0) {
+    float* o = out + 9 * (size_t)w;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) o[k] = v[k];
+    o[6] = mn;
+    o[7] = mx;
+    o[8] = bc;
   }
 }
 
@@ -2975,6 +3004,27 @@ int tcmp_debug_pair_pd(tcmp_handle* h, const int32_t* link, const double* pose,
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(pd, h->s1.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipMemcpyAsync(info, h->i2.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  if (int rc_s = sync_stream(h)) return rc_s;
+  return 0;
+}
+
+int tcmp_debug_wave_reduce(tcmp_handle* h, const float* values, int64_t n, float* out) {
+  TCMP_ENTER(h);
+  if (n < 0 || n > (1 << 20) || (n > 0 && (!values || !out))) return fail(-1, "bad arguments");
+  if (n == 0) return 0;
+  // the scratch buffers hold doubles: two floats each
+  int rc = h->s0.ensure((size_t)n * 64 * 6 / 2);
+  rc = rc ? rc : h->s1.ensure(((size_t)n * 9 + 1) / 2);
+  if (rc) return rc;
+  float* in_d = reinterpret_cast<float*>(h->s0.p);
+  float* out_d = reinterpret_cast<float*>(h->s1.p);
+  HIPCHK(hipMemcpyAsync(in_d, values, (size_t)n * 64 * 6 * sizeof(float), hipMemcpyHostToDevice,
+                        h->stream));
+  hipLaunchKernelGGL(k_debug_wave_reduce, dim3(grid_for(n, 4)), dim3(256), 0, h->stream, in_d,
+                     (int)n, out_d);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(out, out_d, (size_t)n * 9 * sizeof(float), hipMemcpyDeviceToHost,
+                        h->stream));
   if (int rc_s = sync_stream(h)) return rc_s;
   return 0;
 }

@@ -163,10 +163,10 @@ __device__ __forceinline__ float hull_hull_wave32(const HullA32 A, const HullB32
   const unsigned long long tf0 = clock64();
 #endif
   // (1) B's facets (moved into A's frame) against A's vertices (uniform stream)
-  float pd = wave_minf(facets32<true>(A, B, R, p));
+  float pd = wave_minf_fp(facets32<true>(A, B, R, p));
   if (pd < stop) { if (STAT) TCMP_MSTAT(8); TCMP_FCLK(0, tf0); return pd; }
   // (2) A's facets (moved into the world frame) against B's vertices
-  pd = fminf(pd, wave_minf(facets32<false>(A, B, R, p)));
+  pd = fminf(pd, wave_minf_fp(facets32<false>(A, B, R, p)));
   if (pd < stop) { if (STAT) TCMP_MSTAT(9); TCMP_FCLK(0, tf0); return pd; }
 #ifdef TCMP_PROF_EXACT
   const unsigned long long te0 = clock64();
@@ -349,7 +349,7 @@ __device__ __forceinline__ float hull_hull_wave32(const HullA32 A, const HullB32
         }
       }
       if ((w0 + 64 < total || base + 64 < A.e1) && !__ballot(deg)) {
-        const float lf = fminf(pd, wave_minf(loc));
+        const float lf = fminf(pd, wave_minf_fp(loc));
         if (lf < stop) { if (STAT) TCMP_MSTAT(10); TCMP_FCLK(0, tf0); return lf; }
       }
     }
@@ -357,7 +357,7 @@ __device__ __forceinline__ float hull_hull_wave32(const HullA32 A, const HullB32
   TCMP_FCLK(1, tf0 + (clock64() - te0));  // the facet part: te0 - tf0
   TCMP_FCLK(2, te0);
   if (__ballot(deg)) { if (STAT) TCMP_MSTAT(13); return __builtin_nanf(""); }
-  const float res = fminf(pd, wave_minf(loc));
+  const float res = fminf(pd, wave_minf_fp(loc));
   if (STAT) {
     if (res >= (float)kPen) { TCMP_MSTAT(11); } else { TCMP_MSTAT(12); }
   }

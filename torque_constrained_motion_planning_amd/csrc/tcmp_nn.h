@@ -158,11 +158,7 @@ __global__ __launch_bounds__(256) void k_nn_build_supers(DevState* st, const int
     lo[k] = c < c1 ? cbox[16 * c + k] : INFINITY;
     hi[k] = c < c1 ? cbox[16 * c + 8 + k] : -INFINITY;
   }
-#pragma unroll
-  for (int k = 0; k < 7; ++k) {
-    lo[k] = wave_minf(lo[k]);
-    hi[k] = wave_maxf(hi[k]);
-  }
+  wave_minmaxf<7, 7>(lo, hi);
   if (lane_id() == 0) {
 #pragma unroll
     for (int k = 0; k < 7; ++k) {
@@ -189,11 +185,7 @@ __global__ __launch_bounds__(256) void k_nn_build_blocks(DevState* st, const flo
     lo[k] = sp < nsup ? sbox[16 * sp + k] : INFINITY;
     hi[k] = sp < nsup ? sbox[16 * sp + 8 + k] : -INFINITY;
   }
-#pragma unroll
-  for (int k = 0; k < 7; ++k) {
-    lo[k] = wave_minf(lo[k]);
-    hi[k] = wave_maxf(hi[k]);
-  }
+  wave_minmaxf<7, 7>(lo, hi);
   if (lane_id() == 0) {
 #pragma unroll
     for (int k = 0; k < 7; ++k) {
