@@ -405,6 +405,69 @@ int tcmp_plan_retrace(tcmp_handle* h, tcmp_plan_result* result);
  * goal node: res->status = TCMP_PLAN_NO_GOAL and nothing changes. */
 int tcmp_plan_shortcut(tcmp_handle* h, const tcmp_shortcut_cfg* cfg, tcmp_shortcut_result* res);
 
+/* Torque-feasible retiming (no reference counterpart: the reference returns nothing when one
+ * row of the trajectory fails the final torque test, rrt_star.py:208-210).  Playing the same rows
+ * s times slower maps (q, v, a) to (q, v / s, a / s^2), and the rne and dyn torque models are
+ * M a + C(q, v) v + g, so with x = 1 / s^2: tau(q, v sqrt(x), a x) = g(q) + x (tau(q, v, a) - g(q)).
+ * Per row and tested joint j (limits L = 87 87 87 87 12 12, joint 7 untested), with
+ * d = tau - g, sigma = sign(d) and the guard eps = 1e-9 N m:
+ *   d != 0:  ub = ((L - eps) - sigma g) / |d|,  lb = (-(L - eps) - sigma g) / |d|
+ *   d == 0:  ub = +inf, lb = 0 when |g| < L, else ub = -inf, lb = +inf
+ * rne: g = rne(q, 0, 0, m), tau = rne(q, v, a, m), m = mass > 0.01 ? mass : 0; dyn: the same
+ * without payload plus the static Jacobian force term on both; nov: d = 0 (the test ignores the
+ * rates); base: no constraint.  x_hi = min ub, x_lo = max(0, max lb), x_max = 1 / min_scale^2,
+ * x = min(x_max, x_hi), and x = 1.0 exactly when x >= 1 and min_scale == 1.
+ * Status: INFEASIBLE when x <= 0 or x < x_lo; else OVER_CAP when max_scale > 0 and
+ * x < 1 / max_scale^2; else OK, and then r = sqrt(x), s = 1 / r (host, fp64) and
+ * qd' = qd r, qdd' = qdd x, psg' = psg s, one fp64 multiply each (x = 1 keeps every bit).
+ * The scaled rows then go through the ordinary validation of the mode; a failing row there
+ * gives UNVERIFIED and the rows stay as they were (the guard makes that unreachable in
+ * practice).  Deterministic. */
+#define TCMP_RETIME_OK 0
+#define TCMP_RETIME_INFEASIBLE 1     /* no uniform retiming within [min_scale, inf) passes */
+#define TCMP_RETIME_OVER_CAP 2       /* the slow-down needed exceeds max_scale */
+#define TCMP_RETIME_UNVERIFIED 3     /* the scaled rows failed the validation pass */
+#define TCMP_RETIME_NOT_APPLICABLE 4 /* tcmp_plan_retime: nothing to retime (see there) */
+
+typedef struct {
+  double min_scale;          /* (0, 1], 0 = 1; below 1 allows speeding up */
+  double max_scale;          /* >= 1, 0 = no cap */
+} tcmp_retime_cfg;
+
+typedef struct {
+  int32_t status;            /* TCMP_RETIME_* */
+  int32_t bind_joint;        /* lowest joint attaining x_hi on bind_row; -1 when x_hi = +inf */
+  int64_t n_rows;
+  int64_t bind_row;          /* lowest row attaining x_hi; -1 when x_hi = +inf */
+  int64_t n_static;          /* rows with some |g_j| >= L_j - eps */
+  int64_t first_fail_before; /* the validation's first failing row as given, -1 = none */
+  int64_t first_fail_after;  /* of the scaled rows (OK: -1); first_fail_before when not scaled */
+  double x, r, s;            /* x = 1 / s^2, r = sqrt(x), s = 1 / r; 0 unless OK / UNVERIFIED */
+  double x_hi, x_lo;
+  double exec_time_after;    /* tcmp_plan_retime: s * execution_time; else 0 */
+  double ms;                 /* device time of the stage (0 with timing off) */
+} tcmp_retime_result;
+
+/* retime n rows (q, qd, qdd: n x 7; psg: n or NULL) under torque_mode / payload_mass.
+ * qd_out, qdd_out (n x 7) and psg_out (n, NULL iff psg is) are written when the status is OK
+ * and left alone otherwise.  n = 0: OK with x = x_max.  cfg NULL = {1, 0}.  Leaves an open
+ * plan alone. */
+int tcmp_retime_traj(tcmp_handle* h, const double* q, const double* qd, const double* qdd,
+                     const double* psg, int64_t n, int32_t torque_mode, double payload_mass,
+                     const tcmp_retime_cfg* cfg, double* qd_out, double* qdd_out,
+                     double* psg_out, tcmp_retime_result* res);
+
+/* retime the trajectory of the open plan's last tcmp_plan_finish / tcmp_plan_finish_many, with
+ * the plan's own torque mode and payload mass.  Applies when that finish's status was
+ * TCMP_PLAN_OK or TCMP_PLAN_VALIDATION_FAILED; otherwise (no goal, a retrace-only finish, a
+ * min-jerk assert, a shortcut or a retiming since that finish) res->status is
+ * TCMP_RETIME_NOT_APPLICABLE and nothing changes.  On OK the engine's qd, qdd, psg and tau rows
+ * are the scaled ones (tau recomputed from them), its stored status is TCMP_PLAN_OK and its
+ * first_fail -1, so tcmp_plan_fetch returns the retimed trajectory; q and the waypoints are
+ * untouched.  Any other status leaves every row as it was.  The next tcmp_plan_finish or
+ * tcmp_plan_begin discards the retiming; the plan's counters are not touched. */
+int tcmp_plan_retime(tcmp_handle* h, const tcmp_retime_cfg* cfg, tcmp_retime_result* res);
+
 /* copy the finished plan: waypoints (n_waypoints x 7), trajectory q/qd/qdd (n_traj x 7),
  * psg (n_traj), tau = Conf.torques without payload (n_traj x 7).  Any pointer may be NULL. */
 int tcmp_plan_fetch(tcmp_handle* h, double* waypoints, double* q, double* qd, double* qdd,

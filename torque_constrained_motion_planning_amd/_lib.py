@@ -37,6 +37,7 @@ EXPORTS = [
     "tcmp_dist_barrier", "tcmp_dist_allreduce", "tcmp_dist_allgather_i64", "tcmp_gather_paths",
     "tcmp_gather_layout", "tcmp_gather_pack", "tcmp_gather_unpack", "tcmp_dist_rccl_ranks",
     "tcmp_shortcut_path", "tcmp_plan_shortcut",
+    "tcmp_retime_traj", "tcmp_plan_retime",
     "tcmp_tier0_tables", "tcmp_tier0_masks",
     "tcmp_debug_pair_pd", "tcmp_gauss_clusters", "tcmp_debug_wave_reduce",
 ]
@@ -44,6 +45,9 @@ EXPORTS = [
 (PD_CHAIN, PD_BOX32, PD_BOX64, PD_HULL32, PD_HULL64, PD_LOD_IN, PD_LOD_OUT, PD_FACET_AXES,
  PD_SPHERE_CERT) = range(9)
 PD_NO_PRUNE, PD_INNER_BOX = 1, 2
+# tcmp_retime_result.status (include/tcmp.h)
+(RETIME_OK, RETIME_INFEASIBLE, RETIME_OVER_CAP, RETIME_UNVERIFIED,
+ RETIME_NOT_APPLICABLE) = range(5)
 TRAJ_COLS = 22
 REDUCE_SUM, REDUCE_MAX = 0, 1
 
@@ -105,6 +109,27 @@ class ShortcutResult(ctypes.Structure):
         ("chords_tested", ctypes.c_uint64), ("chords_valid", ctypes.c_uint64),
         ("chords_used", ctypes.c_uint64), ("chord_steps", ctypes.c_uint64),
         ("ms", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+class RetimeCfg(ctypes.Structure):
+    """tcmp_retime_cfg"""
+    _fields_ = [("min_scale", ctypes.c_double), ("max_scale", ctypes.c_double)]
+
+
+class RetimeResult(ctypes.Structure):
+    """tcmp_retime_result"""
+    _fields_ = [
+        ("status", ctypes.c_int32), ("bind_joint", ctypes.c_int32),
+        ("n_rows", ctypes.c_int64), ("bind_row", ctypes.c_int64),
+        ("n_static", ctypes.c_int64), ("first_fail_before", ctypes.c_int64),
+        ("first_fail_after", ctypes.c_int64),
+        ("x", ctypes.c_double), ("r", ctypes.c_double), ("s", ctypes.c_double),
+        ("x_hi", ctypes.c_double), ("x_lo", ctypes.c_double),
+        ("exec_time_after", ctypes.c_double), ("ms", ctypes.c_double),
     ]
 
     def as_dict(self):
@@ -203,6 +228,12 @@ def load_library(path=LIB_PATH):
                                              ctypes.c_int64, ctypes.POINTER(ShortcutResult)]
             L.tcmp_plan_shortcut.argtypes = [vp, ctypes.POINTER(ShortcutCfg),
                                              ctypes.POINTER(ShortcutResult)]
+        if hasattr(L, "tcmp_retime_traj"):  # absent from A/B builds of older sources
+            L.tcmp_retime_traj.argtypes = [vp, _dp, _dp, _dp, _dp, ctypes.c_int64, ctypes.c_int32,
+                                           ctypes.c_double, ctypes.POINTER(RetimeCfg), _dp, _dp,
+                                           _dp, ctypes.POINTER(RetimeResult)]
+            L.tcmp_plan_retime.argtypes = [vp, ctypes.POINTER(RetimeCfg),
+                                           ctypes.POINTER(RetimeResult)]
         if hasattr(L, "tcmp_tier0_tables"):  # absent from A/B builds of older sources
             _f32p, _u32p = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_uint32)
             L.tcmp_tier0_tables.argtypes = [_dp, ctypes.c_int32, ctypes.c_int32, _f32p, _u32p, _f32p]
@@ -465,6 +496,39 @@ class Engine:
         cfg = ShortcutCfg(int(max_anchors), int(passes))
         r = ShortcutResult()
         self._check(self.L.tcmp_plan_shortcut(self.h, ctypes.byref(cfg), ctypes.byref(r)))
+        return r
+
+    def retime(self, q, qd, qdd, mode, mass, psg=None, min_scale=1.0, max_scale=0.0):
+        """tcmp_retime_traj: the largest uniform time scaling x = 1 / s^2 under which rows
+        (q, qd r, qdd x), r = sqrt(x), pass the torque test of `mode` -> (qd, qdd, psg | None,
+        RetimeResult).  The rows come back scaled when the status is RETIME_OK and as given
+        otherwise."""
+        if not hasattr(self.L, "tcmp_retime_traj"):
+            raise TcmpError("tcmp_retime_traj: not in this library build")
+        q = _rows(q, "q"); qd = _rows(qd, "qd"); qdd = _rows(qdd, "qdd")
+        if not len(q) == len(qd) == len(qdd):
+            raise ValueError("q, qd and qdd must have the same number of rows")
+        if psg is not None:
+            psg = np.ascontiguousarray(np.asarray(psg, dtype=np.float64).reshape(-1))
+            if len(psg) != len(q):
+                raise ValueError("one psg value per row")
+        cfg = RetimeCfg(float(min_scale), float(max_scale))
+        r = RetimeResult()
+        oqd = qd.copy(); oqdd = qdd.copy()
+        opsg = None if psg is None else psg.copy()
+        self._check(self.L.tcmp_retime_traj(self.h, _d(q), _d(qd), _d(qdd), _d(psg), len(q),
+                                            int(mode), float(mass), ctypes.byref(cfg), _d(oqd),
+                                            _d(oqdd), _d(opsg), ctypes.byref(r)))
+        return oqd, oqdd, opsg, r
+
+    def plan_retime(self, min_scale=1.0, max_scale=0.0):
+        """tcmp_plan_retime: retime the rows of the open plan's last plan_finish; on RETIME_OK
+        plan_fetch returns the retimed trajectory."""
+        if not hasattr(self.L, "tcmp_plan_retime"):
+            raise TcmpError("tcmp_plan_retime: not in this library build")
+        cfg = RetimeCfg(float(min_scale), float(max_scale))
+        r = RetimeResult()
+        self._check(self.L.tcmp_plan_retime(self.h, ctypes.byref(cfg), ctypes.byref(r)))
         return r
 
     def nearest(self, tree, samples, weights=None):

@@ -1317,10 +1317,11 @@ __device__ __forceinline__ void frame_step(double R[9], double p[3], const doubl
 // row is (z_i x (p_target - o_i))_z for joint axis z_i through the URDF joint frame origin
 // o_i; the grasp target sits 0.107 + 0.105 along link7's z axis (the hand only turns about z).
 // The payload mass enters only through the force term, with no 0.01 kg threshold.
+// t: the six tested joints' torques (torque_ok_dyn's test and the retiming bounds read them here)
 template <bool DYN>
-__device__ __forceinline__ bool torque_ok_dyn(const double cq[7], const double sq[7],
-                                              const double qd[7], const double qdd[7],
-                                              double mass) {
+__device__ __forceinline__ void dyn_torques(const double cq[7], const double sq[7],
+                                            const double qd[7], const double qdd[7], double mass,
+                                            double t[6]) {
   double tau[7];
   rne<DYN>(cq, sq, qd, qdd, 0.0, tau);
   double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, p[3] = {0, 0, 0};
@@ -1339,12 +1340,18 @@ __device__ __forceinline__ bool torque_ok_dyn(const double cq[7], const double s
   constexpr double kTarget = kFlangeZ + 0.105;
   const double px = p[0] + R[2] * kTarget, py = p[1] + R[5] * kTarget;
   const double f = mass * 9.81;
+#pragma unroll
+  for (int i = 0; i < 6; ++i) t[i] = tau[i] + f * (zx[i] * (py - oy[i]) - zy[i] * (px - ox[i]));
+}
+template <bool DYN>
+__device__ __forceinline__ bool torque_ok_dyn(const double cq[7], const double sq[7],
+                                              const double qd[7], const double qdd[7],
+                                              double mass) {
+  double t[6];
+  dyn_torques<DYN>(cq, sq, qd, qdd, mass, t);
   bool ok = true;
 #pragma unroll
-  for (int i = 0; i < 6; ++i) {
-    const double t = tau[i] + f * (zx[i] * (py - oy[i]) - zy[i] * (px - ox[i]));
-    ok &= !(fabs(t) >= kEffort[i]);
-  }
+  for (int i = 0; i < 6; ++i) ok &= !(fabs(t[i]) >= kEffort[i]);
   return ok;
 }
 

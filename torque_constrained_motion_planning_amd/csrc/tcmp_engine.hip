@@ -1515,6 +1515,13 @@ struct tcmp_handle {
   DBuf<unsigned char> sc_stats;
   DevState* st_sc = nullptr;
   bool sc_live = false;
+  // torque-feasible retiming (tcmp_retime.h): the stand-alone call's rows, the scaled rows, the
+  // zero rates and static torques of the bounds passes, the blocks' partials; fin_status: the
+  // status of the open plan's last trajectory finish while tcmp_plan_retime may act on its rows
+  // (-1: none, a finish under way, or retimed / shortcut since)
+  DBuf<double> rt_in[4], rt_o[3], rt_zero, rt_g;
+  DBuf<unsigned char> rt_part;
+  int fin_status = -1;
   int edge_split = 4;  // most lanes per edge in small rounds (environment TCMP_EDGE_SPLIT=1/2/4)
   int edge_wps = 2;    // k_edges' persistent grid, blocks per CU (environment TCMP_EDGE_WPS=1/2)
 
@@ -2182,6 +2189,10 @@ int tcmp_destroy(tcmp_handle* h) {
   h->sc_hops.release();
   h->sc_stats.release();
   if (h->st_sc) (void)hipFree(h->st_sc);
+  for (auto* b : {&h->rt_in[0], &h->rt_in[1], &h->rt_in[2], &h->rt_in[3], &h->rt_o[0], &h->rt_o[1],
+                  &h->rt_o[2], &h->rt_zero, &h->rt_g})
+    b->release();
+  h->rt_part.release();
   for (auto e : h->ev_rec) (void)hipEventDestroy(e);
   h->drop_graph();
   for (auto e : h->ev_pool) (void)hipEventDestroy(e);
@@ -3334,6 +3345,7 @@ int plan_begin_launch(tcmp_handle* h, const tcmp_plan_cfg* cfg, tcmp_plan_result
   }
   h->fin_W = 0;
   h->fin_K = 0;
+  h->fin_status = -1;
   h->sc_live = false;
   // one upload and one host wait: the handle's pinned block holds the start / goal rows, the
   // root, the plan state and parameters; k_plan_init scatters them on the device
@@ -3972,6 +3984,7 @@ static int plan_finish_launch(tcmp_handle* h, tcmp_plan_result* r, bool traj) {
   if (!h->plan_open) return fail(-1, "no open plan");
   memset(r, 0, sizeof(*r));
   r->first_fail = -1;
+  h->fin_status = -1;  // (a retiming of the last finish's rows ends here)
   // retrace + min-jerk + validation are launched unconditionally (they do nothing without a
   // goal node) into the buffers tcmp_plan_begin sized, so the host waits once
   hipEvent_t e0;
@@ -4023,6 +4036,7 @@ static int plan_finish_complete(tcmp_handle* h, tcmp_plan_result* r, bool traj) 
     r->goal_found = 1;
     h->fin_W = (size_t)s.W;
     h->fin_K = (size_t)r->n_traj;
+    if (traj) h->fin_status = s.status;
   } else {
     r->status = TCMP_PLAN_NO_GOAL;
   }
@@ -4277,3 +4291,4 @@ int tcmp_plan_debug_round(tcmp_handle* h, int64_t cap, double* cand, int32_t* nn
 
 #include "tcmp_fleet.h"
 #include "tcmp_shortcut.h"
+#include "tcmp_retime.h"

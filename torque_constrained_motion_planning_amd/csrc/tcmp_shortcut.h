@@ -437,6 +437,7 @@ int tcmp_plan_shortcut(tcmp_handle* h, const tcmp_shortcut_cfg* cfg, tcmp_shortc
   if (int rc = sc_cfg(cfg, &a_max, &passes)) return rc;
   memset(res, 0, sizeof(*res));
   h->sc_live = false;
+  h->fin_status = -1;  // the state describes the new list from here, not the finished rows
   hipLaunchKernelGGL(k_retrace, dim3(1), dim3(256), 0, h->stream, h->dP, h->st,
                      Tree{h->cfg.p, h->parent.p, h->tgt.p, h->meta.p}, h->chain.p, h->wp.p,
                      (long long)(h->wp.n / 7));

@@ -51,26 +51,49 @@ def _radius_value(radius):
 
 def rrt_star_force_aware(start, goal, distance, sample, extend, collision, torque_fn, dynam_fn,
                          radius, max_time=INF, max_iterations=INF, goal_probability=.2,
-                         informed=False, shortcut=False):
+                         *positional, retime=False, informed=False, shortcut=False):
     """rrt_star.py:151-211 -> (path, vels, accels, psg) or (None, None, None, None).
+    The positional order is the reference's, then shortcut: a 13th positional argument is
+    `informed` (rrt_star.py:151) and a 14th `shortcut`; retime is keyword-only.
     shortcut (no reference counterpart, off by default): force-aware shortcutting of the
-    retraced path on the device (Engine.plan_shortcut) before dynam_fn; engine loop only."""
+    retraced path on the device (Engine.plan_shortcut) before dynam_fn; engine loop only.
+    retime (no reference counterpart, off by default): a trajectory that fails the final
+    torque validation is played uniformly slower, by the smallest factor that passes
+    (Engine.plan_retime, or Engine.retime on a foreign dynam_fn's rows: velocities / s,
+    accelerations / s^2, psg * s), instead of being dropped; needs the package's torque test.
+    There is no cap on the slow-down here or through Problem(retime=True) (rrt_star_batched
+    has retime_max_scale; Engine.plan_retime / Engine.retime take max_scale)."""
+    if positional:
+        if len(positional) > 2:
+            raise TypeError("rrt_star_force_aware() takes at most 14 positional arguments "
+                            "(%d given)" % (12 + len(positional)))
+        if informed is not False or (len(positional) == 2 and shortcut is not False):
+            raise TypeError("rrt_star_force_aware() got multiple values for argument '%s'"
+                            % ("informed" if informed is not False else "shortcut"))
+        informed = positional[0]
+        if len(positional) == 2:
+            shortcut = positional[1]
     k = _kinds(distance, sample, extend, collision, torque_fn, dynam_fn)
+    if retime and not k["torque"]:
+        raise NotImplementedError(
+            "retime=True needs the package's own torque callback (the torque bounds are "
+            "computed on the device)")
     if k["distance"] and k["extend"] and k["collision"] and k["torque"]:
         res, _, _ = _rrt_engine(start, goal, distance, sample, extend, collision, torque_fn,
                                 dynam_fn, radius, max_iterations, goal_probability, k["dynam"],
-                                informed, shortcut)
+                                informed, shortcut, retime)
         return res
     if shortcut:
         raise NotImplementedError(
             "shortcut=True needs the package's own distance, extend, collision and torque "
             "callbacks (the chords are checked on the device)")
     return _rrt_host(start, goal, distance, sample, extend, collision, torque_fn, dynam_fn,
-                     radius, max_time, max_iterations, goal_probability, informed, k)
+                     radius, max_time, max_iterations, goal_probability, informed, k,
+                     retime=retime)
 
 
 # ---- shared tail: dynam_fn + final validation (rrt_star.py:202-211) --------------------------
-def _validate_and_return(rrt_path, dynam_fn, torque_fn, native_torque):
+def _validate_and_return(rrt_path, dynam_fn, torque_fn, native_torque, retime=False):
     path, psg, vels, accels = dynam_fn(rrt_path, len(rrt_path))
     vels = vels[:len(path)]
     accels = accels[:len(path)]
@@ -82,6 +105,13 @@ def _validate_and_return(rrt_path, dynam_fn, torque_fn, native_torque):
                                                np.asarray(accels, dtype=np.float64)[:, :7],
                                                torque_fn.mode, torque_fn.payload_mass,
                                                want_tau=False)
+        if first_fail >= 0 and retime:
+            v, a, p, rt = _lib.engine().retime(q, np.asarray(vels, dtype=np.float64)[:, :7],
+                                               np.asarray(accels, dtype=np.float64)[:, :7],
+                                               torque_fn.mode, torque_fn.payload_mass, psg=psg)
+            if rt.status != _lib.RETIME_OK:
+                return None, None, None, None
+            return path, [list(x) for x in v], [list(x) for x in a], [float(x) for x in p]
         if first_fail >= 0:
             return None, None, None, None
     else:
@@ -91,10 +121,13 @@ def _validate_and_return(rrt_path, dynam_fn, torque_fn, native_torque):
     return path, vels, accels, psg
 
 
-def _finish(eng, dynam_fn=None, torque_fn=None):
+def _finish(eng, dynam_fn=None, torque_fn=None, retime=None):
     """tcmp_plan_finish -> the reference's return tuple.  dynam_fn: a foreign dynamics fn,
     applied on the host to the engine's retraced waypoints (tcmp_plan_retrace: no device
-    min-jerk or validation runs for it); else the engine's min-jerk and validation stand."""
+    min-jerk or validation runs for it); else the engine's min-jerk and validation stand.
+    retime: None, or the keywords of Engine.plan_retime: a trajectory that fails the validation
+    is retimed and fetched again, and out["retime"] is the RetimeResult (None when the stage did
+    not run); a foreign dynam_fn's rows go through Engine.retime instead."""
     r = eng.plan_retrace() if dynam_fn is not None else eng.plan_finish()
     if r.status == _lib.PLAN_NO_GOAL:
         print("failed to find goal")
@@ -102,11 +135,19 @@ def _finish(eng, dynam_fn=None, torque_fn=None):
     if dynam_fn is not None:
         out = eng.plan_fetch(r)
         rrt_path = [tuple(x) for x in out["waypoints"]]
-        return _validate_and_return(rrt_path, dynam_fn, torque_fn, True), r, out
+        return _validate_and_return(rrt_path, dynam_fn, torque_fn, True,
+                                    retime is not None), r, out
     print("run min jerk")
     if r.status == _lib.PLAN_MINJERK_ASSERT:
         raise AssertionError("Invalid number of intervals chosen (must be greater than 0)")
     out = eng.plan_fetch(r)
+    if retime is not None:
+        out["retime"] = None
+        if r.status == _lib.PLAN_VALIDATION_FAILED:
+            out["retime"] = eng.plan_retime(**retime)
+            if out["retime"].status == _lib.RETIME_OK:
+                r.status, r.first_fail = _lib.PLAN_OK, -1
+                out.update(eng.plan_fetch(r))
     if r.status == _lib.PLAN_VALIDATION_FAILED:
         return (None, None, None, None), r, out
     path = [list(x) for x in out["q"]]
@@ -119,7 +160,7 @@ def _finish(eng, dynam_fn=None, torque_fn=None):
 # ---- engine loop ---------------------------------------------------------------------------
 def _rrt_engine(start, goal, distance, sample, extend, collision, torque_fn, dynam_fn, radius,
                 max_iterations, goal_probability, native_dynam=True, informed=False,
-                shortcut=False):
+                shortcut=False, retime=False):
     if max_iterations == INF:
         raise ValueError("max_iterations must be finite (the reference's time guard never "
                          "fires, rrt_star.py:159, so INF iterations never return)")
@@ -154,17 +195,22 @@ def _rrt_engine(start, goal, distance, sample, extend, collision, torque_fn, dyn
         goal_found = found
     if shortcut:
         eng.plan_shortcut()
-    return _finish(eng, None if native_dynam else dynam_fn, torque_fn)
+    return _finish(eng, None if native_dynam else dynam_fn, torque_fn, {} if retime else None)
 
 
 def rrt_star_batched(start, goal, obstacles, torque_mode, payload_mass, execution_time,
                      n_samples, batch=65536, seed=0, weights=None, resolutions=None,
                      radius=0.01, goal_probability=0.2, device=0, engine=None,
-                     self_collisions=False, shortcut=False, shortcut_passes=1):
+                     self_collisions=False, shortcut=False, shortcut_passes=1, retime=False,
+                     retime_max_scale=0.0):
     """Engine-native batched frontier: n_samples Philox-drawn candidates, `batch` per round
     (self_collisions: the arm's self-collision pairs too, utils.py:3138-3149).
     shortcut: force-aware shortcutting of the path (Engine.plan_shortcut, shortcut_passes
     passes) between the rounds and the finish; its ShortcutResult is raw["shortcut"].
+    retime: when the finish's validation fails (status 3), retime the trajectory on the device
+    (Engine.plan_retime, at most retime_max_scale times slower, 0 = no cap) and return the
+    retimed rows with status 0; raw["retime"] is the RetimeResult (None when the stage did not
+    run).
 
     Returns ((path, vels, accels, psg) | (None,)*4, PlanResult, raw arrays)."""
     from .scene import mesh_pack, obstacle_array
@@ -178,12 +224,15 @@ def rrt_star_batched(start, goal, obstacles, torque_mode, payload_mass, executio
     if st == _lib.PLAN_START_GOAL_COLLISION:
         return (None, None, None, None), None, None
     eng.plan_run(int(n_samples), int(batch))
-    if not shortcut:
-        return _finish(eng)
-    sc = eng.plan_shortcut(passes=shortcut_passes)
-    res, r, raw = _finish(eng)
-    raw = dict(raw) if raw is not None else {}
-    raw["shortcut"] = sc
+    rt = dict(max_scale=retime_max_scale) if retime else None
+    sc = eng.plan_shortcut(passes=shortcut_passes) if shortcut else None
+    res, r, raw = _finish(eng, retime=rt)
+    if shortcut or retime:
+        raw = dict(raw) if raw is not None else {}
+        if shortcut:
+            raw["shortcut"] = sc
+        if retime:
+            raw.setdefault("retime", None)
     return res, r, raw
 
 
@@ -250,7 +299,7 @@ class _Tree:
 
 def _rrt_host(start, goal, distance, sample, extend, collision, torque_fn, dynam_fn, radius,
               max_time=INF, max_iterations=INF, goal_probability=.2, informed=False, kinds=None,
-              stats=None):
+              stats=None, retime=False):
     """rrt_star.py:151-211 with the tree on the host, for foreign distance / extend callbacks.
     Callback call order is the reference's, except that the package's
     own collision and torque tests are evaluated for a whole extend sequence at once (they
@@ -336,4 +385,5 @@ def _rrt_host(start, goal, distance, sample, extend, collision, torque_fn, dynam
     if goal_n is None:
         print("failed to find goal")
         return None, None, None, None
-    return _validate_and_return(tree.retrace(goal_n, extend), dynam_fn, torque_fn, k["torque"])
+    return _validate_and_return(tree.retrace(goal_n, extend), dynam_fn, torque_fn, k["torque"],
+                                retime)

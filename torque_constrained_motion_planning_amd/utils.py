@@ -33,15 +33,19 @@ __all__ = [
 
 
 class Problem:
-    """utils.py:86-93, verbatim fields.  robot: PandaRobot; fixed: [Box]; payload: Payload."""
+    """utils.py:86-93, verbatim fields.  robot: PandaRobot; fixed: [Box]; payload: Payload.
+    retime (no reference counterpart): planner_fn_force_aware retimes a trajectory that fails the
+    final torque validation instead of dropping it (rrt_star_force_aware(retime=True))."""
 
-    def __init__(self, robot, fixed, payload, payload_mass, execution_time, torque_test="arne"):
+    def __init__(self, robot, fixed, payload, payload_mass, execution_time, torque_test="arne",
+                 retime=False):
         self.robot = robot
         self.fixed = fixed
         self.payload = payload
         self.payload_mass = payload_mass
         self.execution_time = execution_time
         self.torque_test = torque_test
+        self.retime = retime
 
 
 def get_arm_joints(robot, arm=None):
