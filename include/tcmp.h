@@ -468,6 +468,84 @@ int tcmp_retime_traj(tcmp_handle* h, const double* q, const double* qd, const do
  * tcmp_plan_begin discards the retiming; the plan's counters are not touched. */
 int tcmp_plan_retime(tcmp_handle* h, const tcmp_retime_cfg* cfg, tcmp_retime_result* res);
 
+/* Collision repair of the min-jerk trajectory (no reference counterpart: the reference's final
+ * validation tests torques only, rrt_star.py:208-210, and so does tcmp_plan_finish).  The edge
+ * checks cover the chords between waypoints; the min-jerk rows leave them, because each joint of
+ * an interior waypoint gets its own velocity (the mean of the adjacent slopes where they agree in
+ * sign, else 0) and so its own time profile inside a segment.
+ * Gated velocity: with a gate g[w] in {0, 1} per waypoint, the velocity of waypoint w is
+ * g[w] ? (tcmp_minjerk's) : 0.0 for all seven joints, and everything else of tcmp_minjerk's
+ * sampling is unchanged, operation for operation; the end waypoints' velocities are 0 whatever
+ * their gates (which stay 1).  Every gate open gives tcmp_minjerk's rows bit for bit; between two
+ * closed gates the rows lie on the chord, x = a + (b - a)(10 t^3 - 15 t^4 + 6 t^5).
+ * A row fails when collision_fn(q_row) is true, as tcmp_check_configs decides it in the scene
+ * set on the handle (joint limits, then boxes and meshes, and the self pairs when enabled).
+ * Passes, from every interior gate open and every segment (rows [s ni, (s + 1) ni)) dirty:
+ *   1. sample and check the ni rows of every dirty segment: hit (any failing row), the first
+ *      failing row, the failing count; a clean segment keeps its last result (no hit);
+ *   2. no segment hit: OK;
+ *   3. a hit segment is stuck when each of its two waypoints is closed or a path end -- a
+ *      rest-to-rest segment whose rows still fail (a collision between the edge check's
+ *      resolution steps, or an end waypoint in collision): UNRESOLVED, with the lowest such
+ *      segment and its first failing row;
+ *   4. max_passes passes run: PASS_CAP;
+ *   5. close g[s] and g[s + 1] of every hit segment s, all at once; the segments next to a gate
+ *      that changed are the next pass's dirty set; again from 1.
+ * Each continuing pass closes at least one gate: at most n_wp - 1 passes.  Two waypoints have no
+ * gate, so any hit is UNRESOLVED.  The closure is greedy, not minimal.  Deterministic. */
+#define TCMP_REPAIR_OK 0
+#define TCMP_REPAIR_UNRESOLVED 1
+#define TCMP_REPAIR_PASS_CAP 2
+#define TCMP_REPAIR_COLLIDES 3        /* check_only: some row fails */
+#define TCMP_REPAIR_NOT_APPLICABLE 4  /* tcmp_plan_repair: nothing to repair (see there) */
+
+typedef struct {
+  int32_t max_passes;        /* 0 = no cap */
+  int32_t check_only;        /* != 0: the first pass only, OK or COLLIDES, nothing written */
+} tcmp_repair_cfg;
+
+typedef struct {
+  int32_t status;            /* TCMP_REPAIR_* */
+  int32_t passes_run;
+  int64_t n_rows, n_segments;
+  int64_t first_hit_before, rows_hit_before; /* rows as plain min-jerk gives them; -1, 0: none */
+  int64_t first_hit_after, rows_hit_after;   /* of the last pass's gates (OK: -1, 0) */
+  int64_t gates_closed, segments_resampled, rows_checked; /* summed over the passes */
+  int64_t stuck_segment, stuck_row;          /* UNRESOLVED, else -1 */
+  int64_t first_fail_before, first_fail_after; /* tcmp_plan_repair: the torque validation's first
+                                                  failing row before / after; else -1 */
+  double ms;                 /* device time of the stage (0 with timing off) */
+} tcmp_repair_result;
+
+/* repair the min-jerk rows of n_wp >= 2 waypoints (n_wp x 7), ni >= 1 samples per segment
+ * (status -1 otherwise), in the scene set on the handle.  q, qd, qdd ((n_wp - 1) ni x 7) and
+ * gates (n_wp) are written when the status is OK and left alone otherwise; with check_only they
+ * may be NULL.  cfg NULL = {0, 0}.  Leaves an open plan alone.  Sized for a planner's paths
+ * (tens to thousands of waypoints): the rows are checked across the whole device, but each pass's
+ * bookkeeping over the segments runs in one workgroup, so a list of millions of waypoints is
+ * accepted (n_wp and ni up to INT_MAX, 2^38 rows) and spends its passes' time there. */
+int tcmp_repair_traj(tcmp_handle* h, const double* waypoints, int64_t n_wp, int64_t ni,
+                     const tcmp_repair_cfg* cfg, double* q, double* qd, double* qdd, int32_t* gates,
+                     tcmp_repair_result* res);
+
+/* repair the trajectory of the open plan's last tcmp_plan_finish / tcmp_plan_finish_many, from
+ * the waypoint list (a shortcut one if stored) and ni that finish used.  Applies when that
+ * finish's status was TCMP_PLAN_OK or TCMP_PLAN_VALIDATION_FAILED and neither a repair that ended
+ * OK nor a retiming that ended TCMP_RETIME_OK has run since; otherwise res->status is
+ * TCMP_REPAIR_NOT_APPLICABLE and nothing changes.  A stage that left every row as it was does
+ * not count: after a repair that ended UNRESOLVED or PASS_CAP, a check_only repair, or a
+ * retiming that ended INFEASIBLE, OVER_CAP or UNVERIFIED, the repair still applies (and may be
+ * repeated, for instance with another max_passes).  OK with no gate closed: the engine is untouched, bit for bit.  OK with gates
+ * closed: the engine's q, qd and qdd rows are the repaired ones (psg and the waypoints are
+ * untouched), the torque validation of the plan's mode and payload mass has run again on them,
+ * tau is recomputed, and the stored status is TCMP_PLAN_OK or TCMP_PLAN_VALIDATION_FAILED with
+ * the new first_fail (res->first_fail_after), so tcmp_plan_fetch returns the repaired trajectory
+ * and tcmp_plan_retime afterwards works on it (rest-to-rest segments accelerate harder, so a
+ * repaired trajectory may need it).  Any other status, and check_only, leave every row as it
+ * was.  Repair then retime is allowed; retime then repair is NOT_APPLICABLE.  The next
+ * tcmp_plan_finish or tcmp_plan_begin discards the repair; the plan's counters are not touched. */
+int tcmp_plan_repair(tcmp_handle* h, const tcmp_repair_cfg* cfg, tcmp_repair_result* res);
+
 /* copy the finished plan: waypoints (n_waypoints x 7), trajectory q/qd/qdd (n_traj x 7),
  * psg (n_traj), tau = Conf.torques without payload (n_traj x 7).  Any pointer may be NULL. */
 int tcmp_plan_fetch(tcmp_handle* h, double* waypoints, double* q, double* qd, double* qdd,

@@ -38,6 +38,7 @@ EXPORTS = [
     "tcmp_gather_layout", "tcmp_gather_pack", "tcmp_gather_unpack", "tcmp_dist_rccl_ranks",
     "tcmp_shortcut_path", "tcmp_plan_shortcut",
     "tcmp_retime_traj", "tcmp_plan_retime",
+    "tcmp_repair_traj", "tcmp_plan_repair",
     "tcmp_tier0_tables", "tcmp_tier0_masks",
     "tcmp_debug_pair_pd", "tcmp_gauss_clusters", "tcmp_debug_wave_reduce",
 ]
@@ -48,6 +49,9 @@ PD_NO_PRUNE, PD_INNER_BOX = 1, 2
 # tcmp_retime_result.status (include/tcmp.h)
 (RETIME_OK, RETIME_INFEASIBLE, RETIME_OVER_CAP, RETIME_UNVERIFIED,
  RETIME_NOT_APPLICABLE) = range(5)
+# tcmp_repair_result.status (include/tcmp.h)
+(REPAIR_OK, REPAIR_UNRESOLVED, REPAIR_PASS_CAP, REPAIR_COLLIDES,
+ REPAIR_NOT_APPLICABLE) = range(5)
 TRAJ_COLS = 22
 REDUCE_SUM, REDUCE_MAX = 0, 1
 
@@ -130,6 +134,29 @@ class RetimeResult(ctypes.Structure):
         ("x", ctypes.c_double), ("r", ctypes.c_double), ("s", ctypes.c_double),
         ("x_hi", ctypes.c_double), ("x_lo", ctypes.c_double),
         ("exec_time_after", ctypes.c_double), ("ms", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+class RepairCfg(ctypes.Structure):
+    """tcmp_repair_cfg"""
+    _fields_ = [("max_passes", ctypes.c_int32), ("check_only", ctypes.c_int32)]
+
+
+class RepairResult(ctypes.Structure):
+    """tcmp_repair_result"""
+    _fields_ = [
+        ("status", ctypes.c_int32), ("passes_run", ctypes.c_int32),
+        ("n_rows", ctypes.c_int64), ("n_segments", ctypes.c_int64),
+        ("first_hit_before", ctypes.c_int64), ("rows_hit_before", ctypes.c_int64),
+        ("first_hit_after", ctypes.c_int64), ("rows_hit_after", ctypes.c_int64),
+        ("gates_closed", ctypes.c_int64), ("segments_resampled", ctypes.c_int64),
+        ("rows_checked", ctypes.c_int64),
+        ("stuck_segment", ctypes.c_int64), ("stuck_row", ctypes.c_int64),
+        ("first_fail_before", ctypes.c_int64), ("first_fail_after", ctypes.c_int64),
+        ("ms", ctypes.c_double),
     ]
 
     def as_dict(self):
@@ -234,6 +261,12 @@ def load_library(path=LIB_PATH):
                                            _dp, ctypes.POINTER(RetimeResult)]
             L.tcmp_plan_retime.argtypes = [vp, ctypes.POINTER(RetimeCfg),
                                            ctypes.POINTER(RetimeResult)]
+        if hasattr(L, "tcmp_repair_traj"):  # absent from A/B builds of older sources
+            L.tcmp_repair_traj.argtypes = [vp, _dp, ctypes.c_int64, ctypes.c_int64,
+                                           ctypes.POINTER(RepairCfg), _dp, _dp, _dp, _i32p,
+                                           ctypes.POINTER(RepairResult)]
+            L.tcmp_plan_repair.argtypes = [vp, ctypes.POINTER(RepairCfg),
+                                           ctypes.POINTER(RepairResult)]
         if hasattr(L, "tcmp_tier0_tables"):  # absent from A/B builds of older sources
             _f32p, _u32p = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_uint32)
             L.tcmp_tier0_tables.argtypes = [_dp, ctypes.c_int32, ctypes.c_int32, _f32p, _u32p, _f32p]
@@ -529,6 +562,37 @@ class Engine:
         cfg = RetimeCfg(float(min_scale), float(max_scale))
         r = RetimeResult()
         self._check(self.L.tcmp_plan_retime(self.h, ctypes.byref(cfg), ctypes.byref(r)))
+        return r
+
+    def repair_traj(self, waypoints, ni, check_only=False, max_passes=0):
+        """tcmp_repair_traj: the min-jerk rows of `waypoints` (n, 7), ni per segment, with the
+        segments whose rows fail collision_fn in this engine's scene put back on their chords
+        (waypoint velocities zeroed) -> (q, qd, qdd, gates, RepairResult).  The arrays are None
+        unless the status is REPAIR_OK (and always with check_only)."""
+        if not hasattr(self.L, "tcmp_repair_traj"):
+            raise TcmpError("tcmp_repair_traj: not in this library build")
+        P = _rows(waypoints, "waypoints")
+        cfg = RepairCfg(int(max_passes), int(bool(check_only)))
+        r = RepairResult()
+        K = max(len(P) - 1, 0) * max(int(ni), 0)
+        q = np.zeros((K, 7)); qd = np.zeros((K, 7)); qdd = np.zeros((K, 7))
+        gates = np.zeros(len(P), dtype=np.int32)
+        self._check(self.L.tcmp_repair_traj(self.h, _d(P), len(P), int(ni), ctypes.byref(cfg),
+                                            _d(q), _d(qd), _d(qdd), gates.ctypes.data_as(_i32p),
+                                            ctypes.byref(r)))
+        if r.status != REPAIR_OK or check_only:
+            return None, None, None, None, r
+        return q, qd, qdd, gates, r
+
+    def plan_repair(self, check_only=False, max_passes=0):
+        """tcmp_plan_repair: collision repair of the rows of the open plan's last plan_finish;
+        on REPAIR_OK with gates closed plan_fetch returns the repaired trajectory (and the
+        engine's stored status is the new torque validation's)."""
+        if not hasattr(self.L, "tcmp_plan_repair"):
+            raise TcmpError("tcmp_plan_repair: not in this library build")
+        cfg = RepairCfg(int(max_passes), int(bool(check_only)))
+        r = RepairResult()
+        self._check(self.L.tcmp_plan_repair(self.h, ctypes.byref(cfg), ctypes.byref(r)))
         return r
 
     def nearest(self, tree, samples, weights=None):

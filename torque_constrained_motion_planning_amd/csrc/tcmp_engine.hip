@@ -989,12 +989,15 @@ __device__ __forceinline__ double gv_at(const double* wp, long long nseg, long l
   return (v0 * v1 >= 1e-10) ? 0.5 * (v0 + v1) : 0.0;
 }
 
+// gates (tcmp_repair.h; null: every gate open, and the tests below fold away): waypoint w's
+// velocity is gv_at's when gates[w] != 0 and 0.0 for all seven joints otherwise
 __device__ __forceinline__ void minjerk_sample(const double* wp, long long nwp, long long ni,
                                                long long i, double x[7], double v[7],
-                                               double a[7]) {
+                                               double a[7], const int* gates = nullptr) {
 #pragma clang fp contract(off)
   const long long nseg = nwp - 1;
   const long long s = i / ni, j = i % ni;
+  const bool g0 = !gates || gates[s] != 0, g1 = !gates || gates[s + 1] != 0;
   const double interval = 1.0 / (double)ni;
   double t;
   if (ni > 1) {
@@ -1008,10 +1011,10 @@ __device__ __forceinline__ void minjerk_sample(const double* wp, long long nwp, 
 #pragma unroll
   for (int k = 0; k < 7; ++k) {
     const double x0 = wp[7 * s + k];
-    const double v0 = s > 0 ? gv_at(wp, nseg, s - 1, k) : 0.0;
+    const double v0 = (s > 0 && g0) ? gv_at(wp, nseg, s - 1, k) : 0.0;
     const double a0 = 0.0;
     const double gx = wp[7 * (s + 1) + k];
-    const double gv = gv_at(wp, nseg, s, k);
+    const double gv = g1 ? gv_at(wp, nseg, s, k) : 0.0;
     const double ga = 0.0;
     const double A = (gx - (x0 + v0 * T + (a0 / 2.0) * T * T)) / (T * T * T);
     const double B = (gv - (v0 + a0 * T)) / (T * T);
@@ -1522,6 +1525,20 @@ struct tcmp_handle {
   DBuf<double> rt_in[4], rt_o[3], rt_zero, rt_g;
   DBuf<unsigned char> rt_part;
   int fin_status = -1;
+  // collision repair (tcmp_repair.h): the stand-alone call's waypoints, the repaired rows, the
+  // gates (two buffers of W, a pass reads one and writes the other), the dirty list, the
+  // segments' first failing row and failing count, the pass summary and the re-validation's
+  // first failing row, and the summary's pinned host copy; fin_first_fail: the last trajectory
+  // finish's; repaired: tcmp_plan_repair has replaced or confirmed that finish's rows (fin_status
+  // stays valid for the retiming)
+  DBuf<double> rp_wp, rp_o[3];
+  DBuf<int> rp_gate[2], rp_dirty;
+  DBuf<unsigned long long> rp_first;
+  DBuf<unsigned> rp_count;
+  DBuf<unsigned char> rp_sum;
+  void* rp_pin = nullptr;
+  long long fin_first_fail = -1;
+  bool repaired = false;
   int edge_split = 4;  // most lanes per edge in small rounds (environment TCMP_EDGE_SPLIT=1/2/4)
   int edge_wps = 2;    // k_edges' persistent grid, blocks per CU (environment TCMP_EDGE_WPS=1/2)
 
@@ -1960,6 +1977,7 @@ PlanParams default_params() {
 
 int upload_spheres(tcmp_handle* h);  // (below) the links' and meshes' inscribed spheres
 int fleet_lds_limits();  // (tcmp_fleet.h) the fused kernels' dynamic-LDS limits, set once
+int repair_lds_limits();  // (tcmp_repair.h) k_repair_rows', likewise
 }  // namespace
 
 // ==========================================================================================
@@ -2097,6 +2115,7 @@ int tcmp_create(int device, tcmp_handle** out) {
                           (const void*)k_rewire_apply<false>, (const void*)k_rewire_apply<true>})
       HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
     if (int rc2 = fleet_lds_limits()) { delete h; return rc2; }
+    if (int rc2 = repair_lds_limits()) { delete h; return rc2; }
   }
   HIPCHK(hipMalloc(&h->st, sizeof(DevState)));
   HIPCHK(hipMemset(h->st, 0, sizeof(DevState)));
@@ -2193,6 +2212,12 @@ int tcmp_destroy(tcmp_handle* h) {
                   &h->rt_o[2], &h->rt_zero, &h->rt_g})
     b->release();
   h->rt_part.release();
+  for (auto* b : {&h->rp_wp, &h->rp_o[0], &h->rp_o[1], &h->rp_o[2]}) b->release();
+  for (auto* b : {&h->rp_gate[0], &h->rp_gate[1], &h->rp_dirty}) b->release();
+  h->rp_first.release();
+  h->rp_count.release();
+  h->rp_sum.release();
+  if (h->rp_pin) (void)hipHostFree(h->rp_pin);
   for (auto e : h->ev_rec) (void)hipEventDestroy(e);
   h->drop_graph();
   for (auto e : h->ev_pool) (void)hipEventDestroy(e);
@@ -3346,6 +3371,7 @@ int plan_begin_launch(tcmp_handle* h, const tcmp_plan_cfg* cfg, tcmp_plan_result
   h->fin_W = 0;
   h->fin_K = 0;
   h->fin_status = -1;
+  h->repaired = false;
   h->sc_live = false;
   // one upload and one host wait: the handle's pinned block holds the start / goal rows, the
   // root, the plan state and parameters; k_plan_init scatters them on the device
@@ -3984,7 +4010,8 @@ static int plan_finish_launch(tcmp_handle* h, tcmp_plan_result* r, bool traj) {
   if (!h->plan_open) return fail(-1, "no open plan");
   memset(r, 0, sizeof(*r));
   r->first_fail = -1;
-  h->fin_status = -1;  // (a retiming of the last finish's rows ends here)
+  h->fin_status = -1;  // (a repair or a retiming of the last finish's rows ends here)
+  h->repaired = false;
   // retrace + min-jerk + validation are launched unconditionally (they do nothing without a
   // goal node) into the buffers tcmp_plan_begin sized, so the host waits once
   hipEvent_t e0;
@@ -4037,6 +4064,7 @@ static int plan_finish_complete(tcmp_handle* h, tcmp_plan_result* r, bool traj) 
     h->fin_W = (size_t)s.W;
     h->fin_K = (size_t)r->n_traj;
     if (traj) h->fin_status = s.status;
+    h->fin_first_fail = s.first_fail;
   } else {
     r->status = TCMP_PLAN_NO_GOAL;
   }
@@ -4292,3 +4320,4 @@ int tcmp_plan_debug_round(tcmp_handle* h, int64_t cap, double* cand, int32_t* nn
 #include "tcmp_fleet.h"
 #include "tcmp_shortcut.h"
 #include "tcmp_retime.h"
+#include "tcmp_repair.h"

@@ -51,10 +51,11 @@ def _radius_value(radius):
 
 def rrt_star_force_aware(start, goal, distance, sample, extend, collision, torque_fn, dynam_fn,
                          radius, max_time=INF, max_iterations=INF, goal_probability=.2,
-                         *positional, retime=False, informed=False, shortcut=False):
+                         *positional, retime=False, repair=False, informed=False,
+                         shortcut=False):
     """rrt_star.py:151-211 -> (path, vels, accels, psg) or (None, None, None, None).
     The positional order is the reference's, then shortcut: a 13th positional argument is
-    `informed` (rrt_star.py:151) and a 14th `shortcut`; retime is keyword-only.
+    `informed` (rrt_star.py:151) and a 14th `shortcut`; retime and repair are keyword-only.
     shortcut (no reference counterpart, off by default): force-aware shortcutting of the
     retraced path on the device (Engine.plan_shortcut) before dynam_fn; engine loop only.
     retime (no reference counterpart, off by default): a trajectory that fails the final
@@ -62,7 +63,12 @@ def rrt_star_force_aware(start, goal, distance, sample, extend, collision, torqu
     (Engine.plan_retime, or Engine.retime on a foreign dynam_fn's rows: velocities / s,
     accelerations / s^2, psg * s), instead of being dropped; needs the package's torque test.
     There is no cap on the slow-down here or through Problem(retime=True) (rrt_star_batched
-    has retime_max_scale; Engine.plan_retime / Engine.retime take max_scale)."""
+    has retime_max_scale; Engine.plan_retime / Engine.retime take max_scale).
+    repair (no reference counterpart, off by default): the min-jerk rows are checked against
+    collision_fn on the device and the segments whose rows collide are put back on their
+    checked chords (Engine.plan_repair) before the validation's verdict is used and before any
+    retiming; a trajectory that still collides is dropped.  Engine loop with the package's own
+    dynamics fn only."""
     if positional:
         if len(positional) > 2:
             raise TypeError("rrt_star_force_aware() takes at most 14 positional arguments "
@@ -78,11 +84,19 @@ def rrt_star_force_aware(start, goal, distance, sample, extend, collision, torqu
         raise NotImplementedError(
             "retime=True needs the package's own torque callback (the torque bounds are "
             "computed on the device)")
+    if repair and not (k["collision"] and k["dynam"]):
+        raise NotImplementedError(
+            "repair=True needs the package's own collision callback and dynamics fn (the rows "
+            "are sampled and checked on the device)")
     if k["distance"] and k["extend"] and k["collision"] and k["torque"]:
         res, _, _ = _rrt_engine(start, goal, distance, sample, extend, collision, torque_fn,
                                 dynam_fn, radius, max_iterations, goal_probability, k["dynam"],
-                                informed, shortcut, retime)
+                                informed, shortcut, retime, repair)
         return res
+    if repair:
+        raise NotImplementedError(
+            "repair=True needs the package's own distance, extend, collision and torque "
+            "callbacks (the trajectory is repaired in the engine's open plan)")
     if shortcut:
         raise NotImplementedError(
             "shortcut=True needs the package's own distance, extend, collision and torque "
@@ -121,13 +135,17 @@ def _validate_and_return(rrt_path, dynam_fn, torque_fn, native_torque, retime=Fa
     return path, vels, accels, psg
 
 
-def _finish(eng, dynam_fn=None, torque_fn=None, retime=None):
+def _finish(eng, dynam_fn=None, torque_fn=None, retime=None, repair=None):
     """tcmp_plan_finish -> the reference's return tuple.  dynam_fn: a foreign dynamics fn,
     applied on the host to the engine's retraced waypoints (tcmp_plan_retrace: no device
     min-jerk or validation runs for it); else the engine's min-jerk and validation stand.
     retime: None, or the keywords of Engine.plan_retime: a trajectory that fails the validation
     is retimed and fetched again, and out["retime"] is the RetimeResult (None when the stage did
-    not run); a foreign dynam_fn's rows go through Engine.retime instead."""
+    not run); a foreign dynam_fn's rows go through Engine.retime instead.
+    repair: None, or the keywords of Engine.plan_repair, run between the finish and the retiming:
+    out["repair"] is the RepairResult; rows it replaced are fetched again with the new
+    validation's verdict, and a trajectory it could not clear is dropped like one that fails the
+    validation."""
     r = eng.plan_retrace() if dynam_fn is not None else eng.plan_finish()
     if r.status == _lib.PLAN_NO_GOAL:
         print("failed to find goal")
@@ -141,6 +159,14 @@ def _finish(eng, dynam_fn=None, torque_fn=None, retime=None):
     if r.status == _lib.PLAN_MINJERK_ASSERT:
         raise AssertionError("Invalid number of intervals chosen (must be greater than 0)")
     out = eng.plan_fetch(r)
+    if repair is not None:
+        rp = out["repair"] = eng.plan_repair(**repair)
+        if rp.status != _lib.REPAIR_OK:
+            return (None, None, None, None), r, out
+        if rp.gates_closed > 0:
+            r.first_fail = rp.first_fail_after
+            r.status = _lib.PLAN_OK if r.first_fail < 0 else _lib.PLAN_VALIDATION_FAILED
+            out.update(eng.plan_fetch(r))
     if retime is not None:
         out["retime"] = None
         if r.status == _lib.PLAN_VALIDATION_FAILED:
@@ -160,7 +186,7 @@ def _finish(eng, dynam_fn=None, torque_fn=None, retime=None):
 # ---- engine loop ---------------------------------------------------------------------------
 def _rrt_engine(start, goal, distance, sample, extend, collision, torque_fn, dynam_fn, radius,
                 max_iterations, goal_probability, native_dynam=True, informed=False,
-                shortcut=False, retime=False):
+                shortcut=False, retime=False, repair=False):
     if max_iterations == INF:
         raise ValueError("max_iterations must be finite (the reference's time guard never "
                          "fires, rrt_star.py:159, so INF iterations never return)")
@@ -195,14 +221,15 @@ def _rrt_engine(start, goal, distance, sample, extend, collision, torque_fn, dyn
         goal_found = found
     if shortcut:
         eng.plan_shortcut()
-    return _finish(eng, None if native_dynam else dynam_fn, torque_fn, {} if retime else None)
+    return _finish(eng, None if native_dynam else dynam_fn, torque_fn, {} if retime else None,
+                   {} if repair else None)
 
 
 def rrt_star_batched(start, goal, obstacles, torque_mode, payload_mass, execution_time,
                      n_samples, batch=65536, seed=0, weights=None, resolutions=None,
                      radius=0.01, goal_probability=0.2, device=0, engine=None,
                      self_collisions=False, shortcut=False, shortcut_passes=1, retime=False,
-                     retime_max_scale=0.0):
+                     retime_max_scale=0.0, *, repair=False):
     """Engine-native batched frontier: n_samples Philox-drawn candidates, `batch` per round
     (self_collisions: the arm's self-collision pairs too, utils.py:3138-3149).
     shortcut: force-aware shortcutting of the path (Engine.plan_shortcut, shortcut_passes
@@ -211,6 +238,9 @@ def rrt_star_batched(start, goal, obstacles, torque_mode, payload_mass, executio
     (Engine.plan_retime, at most retime_max_scale times slower, 0 = no cap) and return the
     retimed rows with status 0; raw["retime"] is the RetimeResult (None when the stage did not
     run).
+    repair: after the finish and before any retiming, collision repair of the min-jerk rows
+    (Engine.plan_repair); raw["repair"] is the RepairResult, and a trajectory that still
+    collides comes back as (None,)*4.
 
     Returns ((path, vels, accels, psg) | (None,)*4, PlanResult, raw arrays)."""
     from .scene import mesh_pack, obstacle_array
@@ -226,7 +256,7 @@ def rrt_star_batched(start, goal, obstacles, torque_mode, payload_mass, executio
     eng.plan_run(int(n_samples), int(batch))
     rt = dict(max_scale=retime_max_scale) if retime else None
     sc = eng.plan_shortcut(passes=shortcut_passes) if shortcut else None
-    res, r, raw = _finish(eng, retime=rt)
+    res, r, raw = _finish(eng, retime=rt, repair={} if repair else None)
     if shortcut or retime:
         raw = dict(raw) if raw is not None else {}
         if shortcut:

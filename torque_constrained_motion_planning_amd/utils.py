@@ -35,10 +35,12 @@ __all__ = [
 class Problem:
     """utils.py:86-93, verbatim fields.  robot: PandaRobot; fixed: [Box]; payload: Payload.
     retime (no reference counterpart): planner_fn_force_aware retimes a trajectory that fails the
-    final torque validation instead of dropping it (rrt_star_force_aware(retime=True))."""
+    final torque validation instead of dropping it (rrt_star_force_aware(retime=True)).
+    repair (no reference counterpart): planner_fn_force_aware collision-checks the min-jerk rows
+    and puts colliding segments back on their chords (rrt_star_force_aware(repair=True))."""
 
     def __init__(self, robot, fixed, payload, payload_mass, execution_time, torque_test="arne",
-                 retime=False):
+                 *, repair=False, retime=False):
         self.robot = robot
         self.fixed = fixed
         self.payload = payload
@@ -46,6 +48,7 @@ class Problem:
         self.execution_time = execution_time
         self.torque_test = torque_test
         self.retime = retime
+        self.repair = repair
 
 
 def get_arm_joints(robot, arm=None):
