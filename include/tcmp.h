@@ -546,6 +546,96 @@ int tcmp_repair_traj(tcmp_handle* h, const double* waypoints, int64_t n_wp, int6
  * tcmp_plan_finish or tcmp_plan_begin discards the repair; the plan's counters are not touched. */
 int tcmp_plan_repair(tcmp_handle* h, const tcmp_repair_cfg* cfg, tcmp_repair_result* res);
 
+/* Per-run torque-feasible retiming (no reference counterpart).  tcmp_retime_traj applies one
+ * scale to every row, decided by the single worst row.  At a waypoint where the arm is at rest
+ * -- all seven velocities 0 (a closed gate, or a natural reversal) and, as at every min-jerk
+ * waypoint, zero acceleration -- the two sides are dynamically decoupled, so each stretch
+ * between rest waypoints (a run) takes its own scale x_k; q is untouched (a repair's collision
+ * verdict stays valid) and the retimed motion stays C^2.
+ * Runs of a waypoint list: interior waypoint w (0 < w < n_wp - 1) is a rest waypoint when
+ * gates != NULL && gates[w] == 0, or when all seven goal velocities of segment w - 1 are 0.0 as
+ * tcmp_minjerk computes them (fp64, no contraction: v0 = (P[w] - P[w-1]) / 1.0,
+ * v1 = (P[w+1] - P[w]) / 1.0, v0 v1 >= 1e-10 ? 0.5 (v0 + v1) : 0.0).  With rest waypoints
+ * w_1 < ... < w_m the runs start at rows 0, w_1 ni, ..., w_m ni and end at (n_wp - 1) ni.
+ * Per run k (rows [run_off[k], run_off[k+1])) everything is tcmp_retime_traj's definition
+ * restricted to the run's rows (ub / lb, the guard, x_hi, x_lo, n_static, ties to the lowest
+ * row, then the lowest joint; bind_row and first_fail are absolute rows): x_k = min(x_max,
+ * x_hi_k), exactly 1.0 when x_k >= 1 and min_scale == 1; the run is INFEASIBLE or OVER_CAP by
+ * the same tests; r_k = sqrt(x_k), s_k = 1 / r_k (host, fp64).  Overall: INFEASIBLE if any run
+ * is, else OVER_CAP if any run is (fail_run: the lowest such run, else -1), and nothing is
+ * written; else every row i of run k gets qd' = qd r_k, qdd' = qdd x_k (one fp64 multiply each:
+ * x_k = 1 keeps every bit), and all scaled rows go through the mode's ordinary torque test (a
+ * failing row: UNVERIFIED, first_fail_after set, outputs left alone).
+ * Time warp (psg given): continuous, piecewise linear, knots at the boundary rows.  Origins
+ * o_0 = psg[0], o_k = psg[run_off[k] - 1]; warped origins on the host in run order, O_0 = o_0,
+ * O_k = O_{k-1} + (o_k - o_{k-1}) s_{k-1}; psg'[i] = O_k + (psg[i] - o_k) s_k (a subtract, a
+ * multiply, an add, no contraction), and psg'[i] = psg[i] when s_k == 1.0 && O_k == o_k, so
+ * leading unscaled runs keep their bits.  Deterministic. */
+typedef struct {
+  int64_t row_begin, row_end; /* the run's rows [row_begin, row_end) */
+  int64_t bind_row;          /* lowest row of the run attaining x_hi; -1 when x_hi = +inf */
+  int64_t first_fail;        /* the run's first row failing the test as given, -1 = none */
+  int64_t n_static;          /* rows of the run with some |g_j| >= L_j - eps */
+  int32_t status;            /* TCMP_RETIME_OK / INFEASIBLE / OVER_CAP, of this run alone */
+  int32_t bind_joint;        /* lowest joint attaining x_hi on bind_row; -1 when x_hi = +inf */
+  double x, r, s;            /* this run's scale; 0 unless the run's status is OK */
+  double x_hi, x_lo;
+  double t_begin;            /* O_k, the warped time at which the run begins; 0 without psg or
+                                when the overall status is INFEASIBLE / OVER_CAP */
+} tcmp_retime_run;
+
+typedef struct {
+  int32_t status;            /* TCMP_RETIME_* */
+  int32_t n_scaled;          /* runs with x_k != 1 */
+  int64_t n_rows, n_runs;
+  int64_t fail_run;          /* lowest INFEASIBLE (else OVER_CAP) run, -1 = none */
+  int64_t first_fail_before; /* the validation's first failing row as given, -1 = none */
+  int64_t first_fail_after;  /* of the scaled rows (OK: -1); first_fail_before when not scaled */
+  double x_min;              /* min x_k: 1 / sqrt(x_min) is tcmp_retime_traj's s at min_scale 1 */
+  double time_ratio;         /* (sum_k s_k rows_k) / n_rows, summed in run order */
+  double exec_time_after;    /* tcmp_plan_retime_runs: execution_time * time_ratio; else 0 */
+  double ms;                 /* device time of the stage (0 with timing off) */
+} tcmp_retime_runs_result;   /* n_scaled, x_min, time_ratio: 0 unless OK / UNVERIFIED; no runs
+                                (n = 0): x_min = x_max, time_ratio = 1 */
+
+/* the runs of n_wp >= 2 waypoints (n_wp x 7), ni >= 1 rows per segment (status -1 otherwise);
+ * gates (n_wp) as tcmp_repair_traj returns them, or NULL = every gate open.  run_off receives
+ * n_runs + 1 ascending row offsets, run_off[0] = 0, run_off[n_runs] = (n_wp - 1) ni.  cap (the
+ * entries run_off holds) below n_runs + 1: status -4 with *n_runs set, run_off untouched.
+ * Host only, no GPU. */
+int tcmp_minjerk_runs(const double* waypoints, int64_t n_wp, int64_t ni, const int32_t* gates,
+                      int64_t* run_off, int64_t cap, int64_t* n_runs);
+
+/* retime n rows (q, qd, qdd: n x 7; psg: n or NULL) run by run.  run_off: n_runs + 1 strictly
+ * ascending offsets with run_off[0] == 0 and run_off[n_runs] == n (status -1 otherwise; n == 0
+ * needs n_runs == 0 and gives OK).  The caller vouches that the boundary rows run_off[k] - 1 are
+ * at rest; the call does not test them (a sampled rest row carries rounding-level
+ * accelerations).  qd_out, qdd_out (n x 7) and psg_out (n, NULL iff psg is) are written when the
+ * status is OK and left alone otherwise; runs (n_runs entries, or NULL) receives the per-run
+ * table whatever the status.  cfg NULL = {1, 0}.  Leaves an open plan alone.  The per-run
+ * reduction gives each run to one wavefront: sized for a planner's runs (thousands of rows); a
+ * single run of many millions of rows is reduced correctly but by 64 lanes. */
+int tcmp_retime_runs_traj(tcmp_handle* h, const double* q, const double* qd, const double* qdd,
+                          const double* psg, int64_t n, const int64_t* run_off, int64_t n_runs,
+                          int32_t torque_mode, double payload_mass, const tcmp_retime_cfg* cfg,
+                          double* qd_out, double* qdd_out, double* psg_out,
+                          tcmp_retime_run* runs, tcmp_retime_runs_result* res);
+
+/* per-run retiming of the open plan's last trajectory finish.  Applies exactly when
+ * tcmp_plan_retime does (that finish ended TCMP_PLAN_OK or TCMP_PLAN_VALIDATION_FAILED and no
+ * OK retiming, of either form, nor a shortcut has run since); otherwise res->status is
+ * TCMP_RETIME_NOT_APPLICABLE and nothing changes.  The runs are tcmp_minjerk_runs of the
+ * waypoint list and ni that finish used, with the gates of the last tcmp_plan_repair that ended
+ * OK with gates closed (kept in a buffer of the plan's own; every gate open without one).
+ * runs (cap_runs entries, or NULL: no table) receives the per-run table; cap_runs below n_runs:
+ * status -4 with res->n_runs set and nothing changed.  On OK it acts as tcmp_plan_retime does:
+ * the engine's qd, qdd and psg rows are the scaled ones, tau is recomputed, the stored status is
+ * TCMP_PLAN_OK with first_fail -1, exec_time_after = execution_time * time_ratio, and
+ * tcmp_plan_retime, tcmp_plan_retime_runs and tcmp_plan_repair are NOT_APPLICABLE until the next
+ * finish.  Any other status leaves every row as it was. */
+int tcmp_plan_retime_runs(tcmp_handle* h, const tcmp_retime_cfg* cfg, tcmp_retime_run* runs,
+                          int64_t cap_runs, tcmp_retime_runs_result* res);
+
 /* copy the finished plan: waypoints (n_waypoints x 7), trajectory q/qd/qdd (n_traj x 7),
  * psg (n_traj), tau = Conf.torques without payload (n_traj x 7).  Any pointer may be NULL. */
 int tcmp_plan_fetch(tcmp_handle* h, double* waypoints, double* q, double* qd, double* qdd,

@@ -39,6 +39,7 @@ EXPORTS = [
     "tcmp_shortcut_path", "tcmp_plan_shortcut",
     "tcmp_retime_traj", "tcmp_plan_retime",
     "tcmp_repair_traj", "tcmp_plan_repair",
+    "tcmp_minjerk_runs", "tcmp_retime_runs_traj", "tcmp_plan_retime_runs",
     "tcmp_tier0_tables", "tcmp_tier0_masks",
     "tcmp_debug_pair_pd", "tcmp_gauss_clusters", "tcmp_debug_wave_reduce",
 ]
@@ -133,6 +134,35 @@ class RetimeResult(ctypes.Structure):
         ("first_fail_after", ctypes.c_int64),
         ("x", ctypes.c_double), ("r", ctypes.c_double), ("s", ctypes.c_double),
         ("x_hi", ctypes.c_double), ("x_lo", ctypes.c_double),
+        ("exec_time_after", ctypes.c_double), ("ms", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+class RetimeRun(ctypes.Structure):
+    """tcmp_retime_run"""
+    _fields_ = [
+        ("row_begin", ctypes.c_int64), ("row_end", ctypes.c_int64),
+        ("bind_row", ctypes.c_int64), ("first_fail", ctypes.c_int64),
+        ("n_static", ctypes.c_int64),
+        ("status", ctypes.c_int32), ("bind_joint", ctypes.c_int32),
+        ("x", ctypes.c_double), ("r", ctypes.c_double), ("s", ctypes.c_double),
+        ("x_hi", ctypes.c_double), ("x_lo", ctypes.c_double), ("t_begin", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+class RetimeRunsResult(ctypes.Structure):
+    """tcmp_retime_runs_result"""
+    _fields_ = [
+        ("status", ctypes.c_int32), ("n_scaled", ctypes.c_int32),
+        ("n_rows", ctypes.c_int64), ("n_runs", ctypes.c_int64), ("fail_run", ctypes.c_int64),
+        ("first_fail_before", ctypes.c_int64), ("first_fail_after", ctypes.c_int64),
+        ("x_min", ctypes.c_double), ("time_ratio", ctypes.c_double),
         ("exec_time_after", ctypes.c_double), ("ms", ctypes.c_double),
     ]
 
@@ -267,6 +297,17 @@ def load_library(path=LIB_PATH):
                                            ctypes.POINTER(RepairResult)]
             L.tcmp_plan_repair.argtypes = [vp, ctypes.POINTER(RepairCfg),
                                            ctypes.POINTER(RepairResult)]
+        if hasattr(L, "tcmp_minjerk_runs"):  # absent from A/B builds of older sources
+            L.tcmp_minjerk_runs.argtypes = [_dp, ctypes.c_int64, ctypes.c_int64, _i32p, _i64p,
+                                            ctypes.c_int64, _i64p]
+            L.tcmp_retime_runs_traj.argtypes = [vp, _dp, _dp, _dp, _dp, ctypes.c_int64, _i64p,
+                                                ctypes.c_int64, ctypes.c_int32, ctypes.c_double,
+                                                ctypes.POINTER(RetimeCfg), _dp, _dp, _dp,
+                                                ctypes.POINTER(RetimeRun),
+                                                ctypes.POINTER(RetimeRunsResult)]
+            L.tcmp_plan_retime_runs.argtypes = [vp, ctypes.POINTER(RetimeCfg),
+                                                ctypes.POINTER(RetimeRun), ctypes.c_int64,
+                                                ctypes.POINTER(RetimeRunsResult)]
         if hasattr(L, "tcmp_tier0_tables"):  # absent from A/B builds of older sources
             _f32p, _u32p = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_uint32)
             L.tcmp_tier0_tables.argtypes = [_dp, ctypes.c_int32, ctypes.c_int32, _f32p, _u32p, _f32p]
@@ -285,6 +326,30 @@ def load_library(path=LIB_PATH):
 
 def _d(a):
     return None if a is None else a.ctypes.data_as(_dp)
+
+
+def minjerk_runs(waypoints, ni, gates=None):
+    """tcmp_minjerk_runs (host only, no GPU): the row offsets (n_runs + 1, int64) of the runs
+    between rest waypoints of the min-jerk rows of `waypoints` (n, 7), ni per segment; gates (n)
+    as Engine.repair_traj returns them, None = every gate open."""
+    L = load_library()
+    if not hasattr(L, "tcmp_minjerk_runs"):
+        raise TcmpError("tcmp_minjerk_runs: not in this library build")
+    P = _rows(waypoints, "waypoints")
+    g = None
+    if gates is not None:
+        g = np.ascontiguousarray(np.asarray(gates, dtype=np.int32).reshape(-1))
+        if len(g) != len(P):
+            raise ValueError("one gate per waypoint")
+    off = np.zeros(max(len(P), 2), dtype=np.int64)
+    n = ctypes.c_int64(0)
+    rc = L.tcmp_minjerk_runs(_d(P), len(P), int(ni),
+                             None if g is None else g.ctypes.data_as(_i32p),
+                             off.ctypes.data_as(_i64p), len(off), ctypes.byref(n))
+    if rc != 0:
+        raise TcmpError("tcmp_minjerk_runs: status %d: %s"
+                        % (rc, (L.tcmp_last_error() or b"").decode()))
+    return off[:n.value + 1].copy()
 
 
 def _rows(x, name="array"):
@@ -563,6 +628,60 @@ class Engine:
         r = RetimeResult()
         self._check(self.L.tcmp_plan_retime(self.h, ctypes.byref(cfg), ctypes.byref(r)))
         return r
+
+    @staticmethod
+    def minjerk_runs(waypoints, ni, gates=None):
+        """tcmp_minjerk_runs: see the module's minjerk_runs (host only)."""
+        return minjerk_runs(waypoints, ni, gates)
+
+    def retime_runs(self, q, qd, qdd, run_off, mode, mass, psg=None, min_scale=1.0,
+                    max_scale=0.0):
+        """tcmp_retime_runs_traj: tcmp_retime_traj with one scale per run (rows
+        [run_off[k], run_off[k + 1]), whose boundary rows the caller vouches are at rest) and a
+        continuous piecewise-linear warp of psg -> (qd, qdd, psg | None, [RetimeRun],
+        RetimeRunsResult).  The rows come back scaled when the status is RETIME_OK and as given
+        otherwise."""
+        if not hasattr(self.L, "tcmp_retime_runs_traj"):
+            raise TcmpError("tcmp_retime_runs_traj: not in this library build")
+        q = _rows(q, "q"); qd = _rows(qd, "qd"); qdd = _rows(qdd, "qdd")
+        if not len(q) == len(qd) == len(qdd):
+            raise ValueError("q, qd and qdd must have the same number of rows")
+        if psg is not None:
+            psg = np.ascontiguousarray(np.asarray(psg, dtype=np.float64).reshape(-1))
+            if len(psg) != len(q):
+                raise ValueError("one psg value per row")
+        off = np.ascontiguousarray(np.asarray(run_off, dtype=np.int64).reshape(-1))
+        n_runs = max(len(off) - 1, 0)
+        cfg = RetimeCfg(float(min_scale), float(max_scale))
+        r = RetimeRunsResult()
+        runs = (RetimeRun * max(n_runs, 1))()
+        oqd = qd.copy(); oqdd = qdd.copy()
+        opsg = None if psg is None else psg.copy()
+        self._check(self.L.tcmp_retime_runs_traj(
+            self.h, _d(q), _d(qd), _d(qdd), _d(psg), len(q), off.ctypes.data_as(_i64p), n_runs,
+            int(mode), float(mass), ctypes.byref(cfg), _d(oqd), _d(oqdd), _d(opsg), runs,
+            ctypes.byref(r)))
+        return oqd, oqdd, opsg, list(runs[:r.n_runs]), r
+
+    def plan_retime_runs(self, min_scale=1.0, max_scale=0.0):
+        """tcmp_plan_retime_runs: per-run retiming of the rows of the open plan's last
+        plan_finish (runs between the waypoints at rest, the gates of an OK plan_repair among
+        them) -> ([RetimeRun], RetimeRunsResult); on RETIME_OK plan_fetch returns the retimed
+        trajectory."""
+        if not hasattr(self.L, "tcmp_plan_retime_runs"):
+            raise TcmpError("tcmp_plan_retime_runs: not in this library build")
+        cfg = RetimeCfg(float(min_scale), float(max_scale))
+        r = RetimeRunsResult()
+        cap = 64
+        while True:
+            runs = (RetimeRun * cap)()
+            rc = self.L.tcmp_plan_retime_runs(self.h, ctypes.byref(cfg), runs, cap,
+                                              ctypes.byref(r))
+            if rc == -4 and r.n_runs > cap:  # nothing has changed: again with room for all
+                cap = int(r.n_runs)
+                continue
+            self._check(rc)
+            return list(runs[:r.n_runs]), r
 
     def repair_traj(self, waypoints, ni, check_only=False, max_passes=0):
         """tcmp_repair_traj: the min-jerk rows of `waypoints` (n, 7), ni per segment, with the

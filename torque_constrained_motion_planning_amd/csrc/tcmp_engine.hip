@@ -1539,7 +1539,17 @@ struct tcmp_handle {
   void* rp_pin = nullptr;
   long long fin_first_fail = -1;
   bool repaired = false;
-  int edge_split = 4;  // most lanes per edge in small rounds (environment TCMP_EDGE_SPLIT=1/2/4)
+  // per-run retiming (tcmp_retime_runs.h): the plan's own copy of the gates its last OK repair
+  // closed (pl_gated: there is one; rp_gate belongs to whichever repair call ran last), the
+  // rows' own intervals, the run offsets ([n_runs, off[0..n_runs]]), the runs' partials, time
+  // origins and (r, x, s, O, o) table, and the host side of the last three
+  DBuf<int> pl_gate;
+  bool pl_gated = false;
+  DBuf<unsigned char> rr_rows, rr_part, rr_tab;
+  DBuf<long long> rr_off;
+  DBuf<double> rr_org;
+  std::vector<unsigned char> rr_host;
+  int edge_split = 4; // most lanes per edge in small rounds (environment TCMP_EDGE_SPLIT=1/2/4)
   int edge_wps = 2;    // k_edges' persistent grid, blocks per CU (environment TCMP_EDGE_WPS=1/2)
 
   Geo geo() const {
@@ -2218,6 +2228,10 @@ int tcmp_destroy(tcmp_handle* h) {
   h->rp_count.release();
   h->rp_sum.release();
   if (h->rp_pin) (void)hipHostFree(h->rp_pin);
+  h->pl_gate.release();
+  for (auto* b : {&h->rr_rows, &h->rr_part, &h->rr_tab}) b->release();
+  h->rr_off.release();
+  h->rr_org.release();
   for (auto e : h->ev_rec) (void)hipEventDestroy(e);
   h->drop_graph();
   for (auto e : h->ev_pool) (void)hipEventDestroy(e);
@@ -3372,6 +3386,7 @@ int plan_begin_launch(tcmp_handle* h, const tcmp_plan_cfg* cfg, tcmp_plan_result
   h->fin_K = 0;
   h->fin_status = -1;
   h->repaired = false;
+  h->pl_gated = false;
   h->sc_live = false;
   // one upload and one host wait: the handle's pinned block holds the start / goal rows, the
   // root, the plan state and parameters; k_plan_init scatters them on the device
@@ -4012,6 +4027,7 @@ static int plan_finish_launch(tcmp_handle* h, tcmp_plan_result* r, bool traj) {
   r->first_fail = -1;
   h->fin_status = -1;  // (a repair or a retiming of the last finish's rows ends here)
   h->repaired = false;
+  h->pl_gated = false;
   // retrace + min-jerk + validation are launched unconditionally (they do nothing without a
   // goal node) into the buffers tcmp_plan_begin sized, so the host waits once
   hipEvent_t e0;
@@ -4321,3 +4337,4 @@ int tcmp_plan_debug_round(tcmp_handle* h, int64_t cap, double* cand, int32_t* nn
 #include "tcmp_shortcut.h"
 #include "tcmp_retime.h"
 #include "tcmp_repair.h"
+#include "tcmp_retime_runs.h"

@@ -375,6 +375,7 @@ int tcmp_plan_repair(tcmp_handle* h, const tcmp_repair_cfg* cfg, tcmp_repair_res
     return 0;
   }
   if (int rc = h->u0.ensure(1)) return rc;
+  if (int rc = h->pl_gate.ensure((size_t)W)) return rc;
   const size_t nb = (size_t)K * 7 * sizeof(double);
   unsigned long long ff = 0;
   // From here the engine's rows change: an error on the way leaves the plan with neither a
@@ -385,6 +386,10 @@ int tcmp_plan_repair(tcmp_handle* h, const tcmp_repair_cfg* cfg, tcmp_repair_res
     HIPCHK(hipMemcpyAsync(h->tq.p, h->rp_o[0].p, nb, hipMemcpyDeviceToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(h->tqd.p, h->rp_o[1].p, nb, hipMemcpyDeviceToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(h->tqdd.p, h->rp_o[2].p, nb, hipMemcpyDeviceToDevice, h->stream));
+    // the plan's own copy of the gates (tcmp_plan_retime_runs derives its runs from them; a
+    // later stand-alone tcmp_repair_traj on this handle overwrites rp_gate)
+    HIPCHK(hipMemcpyAsync(h->pl_gate.p, h->rp_gate[cur].p, (size_t)W * sizeof(int),
+                          hipMemcpyDeviceToDevice, h->stream));
     HIPCHK(hipMemsetAsync(h->u0.p, 0xff, sizeof(ff), h->stream));
     hipLaunchKernelGGL(TCMP_BY_MODE(k_rp_validate, h->P.torque_mode), dim3(grid_for(K, 256)),
                        dim3(256), 0, h->stream, h->tq.p, h->tqd.p, h->tqdd.p, K, h->P.mass,
@@ -410,6 +415,7 @@ int tcmp_plan_repair(tcmp_handle* h, const tcmp_repair_cfg* cfg, tcmp_repair_res
   h->pin->st.status = h->fin_status;
   h->pin->st.first_fail = res->first_fail_after;
   h->repaired = true;
+  h->pl_gated = true;
   return 0;
 }
 

@@ -29,6 +29,15 @@ struct RtPart {
   int pad;
 };
 
+// a row's own interval (k_rt_bounds' optional record, the input of the per-run reduction in
+// tcmp_retime_runs.h): ub / lb over the six joints, the lowest joint attaining ub, and
+// flags bit 0: some |g_j| >= L_j - eps, bit 1: the row fails the test as given
+struct RtRow {
+  double ub, lb;
+  int jb;
+  int flags;
+};
+
 // the six tested joints' torques as the mode's test sees them: the calls torque_test_m makes
 // (torque_ok, torque_ok_dyn), stopped before the comparison with the limits
 template <int MODE>
@@ -56,13 +65,14 @@ __device__ __forceinline__ void rt_torques(double mass, const double cq[7], cons
 // k_rt_bounds: one row per thread (rows of 7).  pass 0: the row's torques to g (rows of 6).
 // pass 1: the row's interval against g, the wave's minimum / maximum (DPP), the block's
 // partial.  Ties of x_hi go to the lowest row, then the lowest joint: lanes and waves are
-// scanned in row order with a strict <.
+// scanned in row order with a strict <.  rows (null on the uniform path): every row's own
+// interval as well, from this same instruction stream.
 // ------------------------------------------------------------------------------------------
 template <int MODE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE >= 2 ? 1 : 2)))
 void k_rt_bounds(const double* __restrict__ q, const double* __restrict__ qd,
                  const double* __restrict__ qdd, long long n, double mass, int pass, double* g,
-                 RtPart* part) {
+                 RtPart* part, RtRow* rows) {
   __shared__ RtPart wp[4];
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   const bool act = i < n;
@@ -117,6 +127,14 @@ void k_rt_bounds(const double* __restrict__ q, const double* __restrict__ qd,
       lb = fmax(lb, l);
       stat |= fabs(gj) >= Lg;
       bad |= fabs(tj) >= L;
+    }
+    if (rows) {
+      RtRow w;
+      w.ub = ub;
+      w.lb = lb;
+      w.jb = jb;
+      w.flags = (stat ? 1 : 0) | (bad ? 2 : 0);
+      rows[i] = w;
     }
   }
   const int lane = lane_id(), wave = threadIdx.x >> 6;
@@ -272,9 +290,9 @@ int rt_run(tcmp_handle* h, const double* q, const double* qd, const double* qdd,
     if (rc) return rc;
     HIPCHK(hipMemsetAsync(h->rt_zero.p, 0, (size_t)n * 7 * sizeof(double), h->stream));
     hipLaunchKernelGGL(TCMP_BY_MODE(k_rt_bounds, mode), dim3(nb), dim3(256), 0, h->stream, q,
-                       h->rt_zero.p, h->rt_zero.p, n, mass, 0, h->rt_g.p, dpart);
+                       h->rt_zero.p, h->rt_zero.p, n, mass, 0, h->rt_g.p, dpart, (RtRow*)nullptr);
     hipLaunchKernelGGL(TCMP_BY_MODE(k_rt_bounds, mode), dim3(nb), dim3(256), 0, h->stream, q, qd,
-                       qdd, n, mass, 1, h->rt_g.p, dpart);
+                       qdd, n, mass, 1, h->rt_g.p, dpart, (RtRow*)nullptr);
     hipLaunchKernelGGL(k_rt_reduce, dim3(1), dim3(256), 0, h->stream, dpart, (int)nb, dpart + nb);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(&p, dpart + nb, sizeof(p), hipMemcpyDeviceToHost, h->stream));

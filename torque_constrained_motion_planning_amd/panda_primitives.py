@@ -193,7 +193,7 @@ def planner_fn_force_aware(start_conf, pose, problem):
         robot, arm_joints, grasp_conf, torque_test, dynam_fn, attachments=[],
         obstacles=obstacles, self_collisions=SELF_COLLISIONS, max_time=50, custom_limits={},
         radius=resolutions / 2, max_iterations=50, start_conf=start_conf,
-        **({"retime": True} if getattr(problem, "retime", False) else {}),
+        **({"retime": problem.retime} if getattr(problem, "retime", False) else {}),
         **({"repair": True} if getattr(problem, "repair", False) else {}))
     approach_path, approach_vels, approach_accels, approach_dts = res  # 3-tuple -> ValueError (sic)
     if approach_path is None:

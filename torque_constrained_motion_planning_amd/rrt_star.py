@@ -64,6 +64,11 @@ def rrt_star_force_aware(start, goal, distance, sample, extend, collision, torqu
     accelerations / s^2, psg * s), instead of being dropped; needs the package's torque test.
     There is no cap on the slow-down here or through Problem(retime=True) (rrt_star_batched
     has retime_max_scale; Engine.plan_retime / Engine.retime take max_scale).
+    retime="runs": the retiming is per run instead -- every stretch between waypoints at rest
+    (the gates a repair closed, reversals of all seven joints) gets its own factor and psg a
+    continuous piecewise-linear warp (Engine.plan_retime_runs); engine loop with the package's
+    own dynamics fn only (a foreign dynam_fn's rows have no waypoints or gates to derive runs
+    from: ValueError).
     repair (no reference counterpart, off by default): the min-jerk rows are checked against
     collision_fn on the device and the segments whose rows collide are put back on their
     checked chords (Engine.plan_repair) before the validation's verdict is used and before any
@@ -80,6 +85,11 @@ def rrt_star_force_aware(start, goal, distance, sample, extend, collision, torqu
         if len(positional) == 2:
             shortcut = positional[1]
     k = _kinds(distance, sample, extend, collision, torque_fn, dynam_fn)
+    _retime_kw(retime)
+    if retime == "runs" and not k["dynam"]:
+        raise ValueError(
+            'retime="runs" needs the package\'s own dynamics fn (a foreign dynam_fn\'s rows have '
+            'no waypoints or gates to derive runs from)')
     if retime and not k["torque"]:
         raise NotImplementedError(
             "retime=True needs the package's own torque callback (the torque bounds are "
@@ -101,9 +111,25 @@ def rrt_star_force_aware(start, goal, distance, sample, extend, collision, torqu
         raise NotImplementedError(
             "shortcut=True needs the package's own distance, extend, collision and torque "
             "callbacks (the chords are checked on the device)")
+    if retime == "runs":
+        raise NotImplementedError(
+            "retime=\"runs\" needs the package's own distance, extend, collision and torque "
+            "callbacks (the runs are derived from the engine's open plan)")
     return _rrt_host(start, goal, distance, sample, extend, collision, torque_fn, dynam_fn,
                      radius, max_time, max_iterations, goal_probability, informed, k,
                      retime=retime)
+
+
+def _retime_kw(retime, **kw):
+    """The retime argument of the drop-ins -> _finish's: None (off), or the keywords of the
+    stage, with runs=True for the per-run form."""
+    if retime is False or retime is None:
+        return None
+    if retime is True:
+        return dict(kw)
+    if retime == "runs":
+        return dict(kw, runs=True)
+    raise ValueError('retime must be False, True or "runs" (got %r)' % (retime,))
 
 
 # ---- shared tail: dynam_fn + final validation (rrt_star.py:202-211) --------------------------
@@ -141,11 +167,20 @@ def _finish(eng, dynam_fn=None, torque_fn=None, retime=None, repair=None):
     min-jerk or validation runs for it); else the engine's min-jerk and validation stand.
     retime: None, or the keywords of Engine.plan_retime: a trajectory that fails the validation
     is retimed and fetched again, and out["retime"] is the RetimeResult (None when the stage did
-    not run); a foreign dynam_fn's rows go through Engine.retime instead.
+    not run); a foreign dynam_fn's rows go through Engine.retime instead.  With runs=True among
+    them the stage is Engine.plan_retime_runs: out["retime"] is the RetimeRunsResult and
+    out["retime_runs"] the per-run table.
     repair: None, or the keywords of Engine.plan_repair, run between the finish and the retiming:
     out["repair"] is the RepairResult; rows it replaced are fetched again with the new
     validation's verdict, and a trajectory it could not clear is dropped like one that fails the
     validation."""
+    by_runs = False
+    if retime is not None:
+        retime = dict(retime)
+        by_runs = bool(retime.pop("runs", False))
+    if by_runs and dynam_fn is not None:
+        raise ValueError('retime="runs" needs the engine\'s own min-jerk (no waypoints or gates '
+                         "to derive runs from)")
     r = eng.plan_retrace() if dynam_fn is not None else eng.plan_finish()
     if r.status == _lib.PLAN_NO_GOAL:
         print("failed to find goal")
@@ -169,8 +204,13 @@ def _finish(eng, dynam_fn=None, torque_fn=None, retime=None, repair=None):
             out.update(eng.plan_fetch(r))
     if retime is not None:
         out["retime"] = None
+        if by_runs:
+            out["retime_runs"] = None
         if r.status == _lib.PLAN_VALIDATION_FAILED:
-            out["retime"] = eng.plan_retime(**retime)
+            if by_runs:
+                out["retime_runs"], out["retime"] = eng.plan_retime_runs(**retime)
+            else:
+                out["retime"] = eng.plan_retime(**retime)
             if out["retime"].status == _lib.RETIME_OK:
                 r.status, r.first_fail = _lib.PLAN_OK, -1
                 out.update(eng.plan_fetch(r))
@@ -221,7 +261,7 @@ def _rrt_engine(start, goal, distance, sample, extend, collision, torque_fn, dyn
         goal_found = found
     if shortcut:
         eng.plan_shortcut()
-    return _finish(eng, None if native_dynam else dynam_fn, torque_fn, {} if retime else None,
+    return _finish(eng, None if native_dynam else dynam_fn, torque_fn, _retime_kw(retime),
                    {} if repair else None)
 
 
@@ -237,13 +277,15 @@ def rrt_star_batched(start, goal, obstacles, torque_mode, payload_mass, executio
     retime: when the finish's validation fails (status 3), retime the trajectory on the device
     (Engine.plan_retime, at most retime_max_scale times slower, 0 = no cap) and return the
     retimed rows with status 0; raw["retime"] is the RetimeResult (None when the stage did not
-    run).
+    run).  retime="runs": per run between the waypoints at rest (Engine.plan_retime_runs);
+    raw["retime"] is the RetimeRunsResult and raw["retime_runs"] the per-run table.
     repair: after the finish and before any retiming, collision repair of the min-jerk rows
     (Engine.plan_repair); raw["repair"] is the RepairResult, and a trajectory that still
     collides comes back as (None,)*4.
 
     Returns ((path, vels, accels, psg) | (None,)*4, PlanResult, raw arrays)."""
     from .scene import mesh_pack, obstacle_array
+    rt = _retime_kw(retime, max_scale=retime_max_scale)
     eng = engine if engine is not None else _lib.engine(device)
     eng.set_scene(obstacle_array(obstacles), mesh_pack(obstacles))
     eng.set_self_collision(self_collisions)
@@ -254,7 +296,6 @@ def rrt_star_batched(start, goal, obstacles, torque_mode, payload_mass, executio
     if st == _lib.PLAN_START_GOAL_COLLISION:
         return (None, None, None, None), None, None
     eng.plan_run(int(n_samples), int(batch))
-    rt = dict(max_scale=retime_max_scale) if retime else None
     sc = eng.plan_shortcut(passes=shortcut_passes) if shortcut else None
     res, r, raw = _finish(eng, retime=rt, repair={} if repair else None)
     if shortcut or retime:
@@ -263,6 +304,8 @@ def rrt_star_batched(start, goal, obstacles, torque_mode, payload_mass, executio
             raw["shortcut"] = sc
         if retime:
             raw.setdefault("retime", None)
+        if retime == "runs":
+            raw.setdefault("retime_runs", None)
     return res, r, raw
 
 

@@ -35,7 +35,8 @@ __all__ = [
 class Problem:
     """utils.py:86-93, verbatim fields.  robot: PandaRobot; fixed: [Box]; payload: Payload.
     retime (no reference counterpart): planner_fn_force_aware retimes a trajectory that fails the
-    final torque validation instead of dropping it (rrt_star_force_aware(retime=True)).
+    final torque validation instead of dropping it (rrt_star_force_aware(retime=True));
+    retime="runs": per run between the waypoints at rest (rrt_star_force_aware(retime="runs")).
     repair (no reference counterpart): planner_fn_force_aware collision-checks the min-jerk rows
     and puts colliding segments back on their chords (rrt_star_force_aware(repair=True))."""
 
