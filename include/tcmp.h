@@ -660,6 +660,47 @@ int tcmp_plan_tree(tcmp_handle* h, int64_t cap, double* cfg, double* cost, int32
 int tcmp_plan_debug_round(tcmp_handle* h, int64_t cap, double* cand, int32_t* nn,
                           double* score, int64_t* snap, int32_t* nb);
 
+/* ---- torque-aware goal search over the IK redundancy (opt-in) --------------------------- */
+/* The reference turns a grasp pose into one goal configuration by taking the first free value
+ * (joint 7) with any limit-valid IK solution, one of those at random, a body collision check and
+ * up to 25 retries, and runs the static torque test once on what survived
+ * (panda_primitives.py:240-265); tcmp_ik replays that.  tcmp_goal_search evaluates EVERY
+ * candidate instead.  Candidate id = f * 8 + k of pose p is slot k of
+ * tcmp_ik(poses[p], free_q7[f]), k < that call's count, and its configuration is tcmp_ik's bit
+ * for bit (the same kernel runs).  Filters, in order:
+ *   limits     every joint within the limits, inclusive (collision_fn's test);
+ *   torque     the six tested torques as the mode's test sees them at rest (zero rates): the
+ *              candidate passes iff every !(|t_j| >= L_j), tcmp_torque_ok's comparison (a NaN
+ *              fails); headroom = min_j (L_j - |t_j|) / L_j, 1.0 in TCMP_TORQUE_BASE;
+ *   collision  the candidate collides iff tcmp_check_body or tcmp_check_configs says so in the
+ *              scene on the handle: moving links against boxes and meshes, the self pairs when
+ *              enabled, and the base link panda_link0, whose verdict is q-independent.
+ * The feasible candidates of a pose are ordered by ascending (distance, id), distance =
+ * sqrt(sum_k w_k (q_k - ref_k)^2) summed in joint order without contraction (the planner's
+ * metric); the first n_out go to rows p * max_out + i of the outputs, the other rows are zeros
+ * with id -1.  Headroom is reported, never a sort key: mirror branches (q1 + pi, -q2, q3 + pi)
+ * have equal gravity torques up to rounding.  The result is deterministic (equal calls give equal
+ * bytes), and the call leaves an open plan alone. */
+typedef struct {
+  int64_t n_solutions;   /* sum of tcmp_ik's counts over the free values */
+  int64_t n_in_limits;   /* ... whose seven joints are within the limits */
+  int64_t n_torque_ok;   /* ... and pass the mode's static torque test */
+  int64_t n_feasible;    /* ... and are collision free */
+  int32_t n_out;         /* min(n_feasible, max_out) */
+  int32_t base_collides; /* panda_link0 collides with the scene: no candidate can be feasible */
+} tcmp_goal_stats;
+
+/* poses n_pose x 12 (as tcmp_ik takes them), free_q7 n_free values shared by all poses, ref 7,
+ * weights 7 or NULL (10 each), max_out 1..256; n_pose >= 1, n_free >= 1 and
+ * n_pose * n_free * 8 < 2^31, else status -1.  Outputs, each may be NULL: q_out
+ * (n_pose * max_out x 7), dist_out, headroom_out, id_out (n_pose * max_out), stats (n_pose, one
+ * per pose), ms (the device time of the stage).  One host wait. */
+int tcmp_goal_search(tcmp_handle* h, const double* poses, int32_t n_pose,
+                     const double* free_q7, int32_t n_free, const double* ref,
+                     const double* weights, int32_t torque_mode, double payload_mass,
+                     int32_t max_out, double* q_out, double* dist_out, double* headroom_out,
+                     int32_t* id_out, tcmp_goal_stats* stats, double* ms);
+
 /* ---- multi-GPU: query sharding + RCCL gather of solved paths -------------- */
 /* One process per GPU; independent queries are dealt to ranks (collect_data.py:74-85 plans
  * them in a loop); the only collective is the gather of solved trajectories to rank 0.

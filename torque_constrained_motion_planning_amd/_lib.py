@@ -42,6 +42,7 @@ EXPORTS = [
     "tcmp_minjerk_runs", "tcmp_retime_runs_traj", "tcmp_plan_retime_runs",
     "tcmp_tier0_tables", "tcmp_tier0_masks",
     "tcmp_debug_pair_pd", "tcmp_gauss_clusters", "tcmp_debug_wave_reduce",
+    "tcmp_goal_search",
 ]
 # tcmp_debug_pair_pd: stages of the pair-depth chain and its flags (include/tcmp.h)
 (PD_CHAIN, PD_BOX32, PD_BOX64, PD_HULL32, PD_HULL64, PD_LOD_IN, PD_LOD_OUT, PD_FACET_AXES,
@@ -193,6 +194,18 @@ class RepairResult(ctypes.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class GoalStats(ctypes.Structure):
+    """tcmp_goal_stats"""
+    _fields_ = [
+        ("n_solutions", ctypes.c_int64), ("n_in_limits", ctypes.c_int64),
+        ("n_torque_ok", ctypes.c_int64), ("n_feasible", ctypes.c_int64),
+        ("n_out", ctypes.c_int32), ("base_collides", ctypes.c_int32),
+    ]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 class TcmpError(RuntimeError):
     pass
 
@@ -320,6 +333,10 @@ def load_library(path=LIB_PATH):
         if hasattr(L, "tcmp_debug_wave_reduce"):  # absent from A/B builds of older sources
             _f32p = ctypes.POINTER(ctypes.c_float)
             L.tcmp_debug_wave_reduce.argtypes = [vp, _f32p, ctypes.c_int64, _f32p]
+        if hasattr(L, "tcmp_goal_search"):  # absent from A/B builds of older sources
+            L.tcmp_goal_search.argtypes = [vp, _dp, ctypes.c_int32, _dp, ctypes.c_int32, _dp, _dp,
+                                           ctypes.c_int32, ctypes.c_double, ctypes.c_int32, _dp,
+                                           _dp, _dp, _i32p, ctypes.POINTER(GoalStats), _dp]
         _lib = L
         return L
 
@@ -467,6 +484,34 @@ class Engine:
         self._check(self.L.tcmp_ik(self.h, _d(poses), _d(free_q7), len(poses), _d(sols),
                                    cnt.ctypes.data_as(_i32p)))
         return sols, cnt
+
+    def goal_search(self, poses, free_q7, ref, mode, mass, weights=None, max_out=8):
+        """tcmp_goal_search: every IK candidate (free value f, slot k; id = f * 8 + k) of every
+        pose through the limits, the mode's static torque test and the scene's collision check,
+        the feasible ones ordered by (distance from ref, id).  poses (n, 12) or (n, 4, 4),
+        free_q7 (n_free,) shared by the poses.  Returns (q (n, max_out, 7), dist (n, max_out),
+        headroom (n, max_out), ids (n, max_out; -1 past a pose's n_out), stats: one GoalStats
+        per pose); self.goal_ms holds the stage's device time."""
+        if not hasattr(self.L, "tcmp_goal_search"):
+            raise TcmpError("tcmp_goal_search: not in this library build")
+        poses = pose_rows(poses)
+        free_q7 = np.ascontiguousarray(np.asarray(free_q7, dtype=np.float64).reshape(-1))
+        ref = np.ascontiguousarray(np.asarray(ref, dtype=np.float64).reshape(7))
+        w = None if weights is None else np.ascontiguousarray(
+            np.asarray(weights, dtype=np.float64).reshape(7))
+        n, m = len(poses), int(max_out)
+        q = np.zeros((n, max(m, 0), 7))
+        dist = np.zeros((n, max(m, 0)))
+        head = np.zeros((n, max(m, 0)))
+        ids = np.full((n, max(m, 0)), -1, dtype=np.int32)
+        stats = (GoalStats * max(n, 1))()
+        ms = ctypes.c_double(0.0)
+        self._check(self.L.tcmp_goal_search(self.h, _d(poses), n, _d(free_q7), len(free_q7),
+                                            _d(ref), _d(w), int(mode), float(mass), m, _d(q),
+                                            _d(dist), _d(head), ids.ctypes.data_as(_i32p), stats,
+                                            ctypes.byref(ms)))
+        self.goal_ms = ms.value
+        return q, dist, head, ids, list(stats)[:n]
 
     def debug_counters(self, n=8):
         out = (ctypes.c_uint64 * n)()

@@ -1549,6 +1549,15 @@ struct tcmp_handle {
   DBuf<long long> rr_off;
   DBuf<double> rr_org;
   std::vector<unsigned char> rr_host;
+  // goal search (tcmp_goal.h): the poses, free values and (ref, weights) as given, their
+  // per-(pose, free value) expansion for k_ik, its solutions and counts, the slots' keys
+  // (distance bits, all ones: not feasible) and headrooms, the torque stage's work list, the
+  // poses' feasible lists in slot order, the counters ([list length, base flag], then four per
+  // pose) and the output rows
+  DBuf<double> gs_pose, gs_free, gs_refw, gs_xpose, gs_xfree, gs_sol, gs_head, gs_out;
+  DBuf<int> gs_cnt, gs_list, gs_lid, gs_oid;
+  DBuf<unsigned long long> gs_key, gs_lkey, gs_ctr;
+  double gs_refw_h[14] = {};  // (ref, weights) on the host until their upload has run
   int edge_split = 4; // most lanes per edge in small rounds (environment TCMP_EDGE_SPLIT=1/2/4)
   int edge_wps = 2;    // k_edges' persistent grid, blocks per CU (environment TCMP_EDGE_WPS=1/2)
 
@@ -1988,6 +1997,7 @@ PlanParams default_params() {
 int upload_spheres(tcmp_handle* h);  // (below) the links' and meshes' inscribed spheres
 int fleet_lds_limits();  // (tcmp_fleet.h) the fused kernels' dynamic-LDS limits, set once
 int repair_lds_limits();  // (tcmp_repair.h) k_repair_rows', likewise
+int goal_lds_limits();    // (tcmp_goal.h) k_goal_collide's, likewise
 }  // namespace
 
 // ==========================================================================================
@@ -2126,6 +2136,7 @@ int tcmp_create(int device, tcmp_handle** out) {
       HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
     if (int rc2 = fleet_lds_limits()) { delete h; return rc2; }
     if (int rc2 = repair_lds_limits()) { delete h; return rc2; }
+    if (int rc2 = goal_lds_limits()) { delete h; return rc2; }
   }
   HIPCHK(hipMalloc(&h->st, sizeof(DevState)));
   HIPCHK(hipMemset(h->st, 0, sizeof(DevState)));
@@ -2232,6 +2243,11 @@ int tcmp_destroy(tcmp_handle* h) {
   for (auto* b : {&h->rr_rows, &h->rr_part, &h->rr_tab}) b->release();
   h->rr_off.release();
   h->rr_org.release();
+  for (auto* b : {&h->gs_pose, &h->gs_free, &h->gs_refw, &h->gs_xpose, &h->gs_xfree, &h->gs_sol,
+                  &h->gs_head, &h->gs_out})
+    b->release();
+  for (auto* b : {&h->gs_cnt, &h->gs_list, &h->gs_lid, &h->gs_oid}) b->release();
+  for (auto* b : {&h->gs_key, &h->gs_lkey, &h->gs_ctr}) b->release();
   for (auto e : h->ev_rec) (void)hipEventDestroy(e);
   h->drop_graph();
   for (auto e : h->ev_pool) (void)hipEventDestroy(e);
@@ -4338,3 +4354,4 @@ int tcmp_plan_debug_round(tcmp_handle* h, int64_t cap, double* cand, int32_t* nn
 #include "tcmp_retime.h"
 #include "tcmp_repair.h"
 #include "tcmp_retime_runs.h"
+#include "tcmp_goal.h"

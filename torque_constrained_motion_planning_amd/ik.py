@@ -266,3 +266,40 @@ def grasp_conf_for_pose(problem, start_conf, pose, engine=None, rng=None, shuffl
         if conf is not None:
             return tuple(float(v) for v in conf)
     return None
+
+
+# ---- torque-aware goal search (no reference counterpart; opt-in) -------------------------------
+
+
+def free_grid(current_q7, n):
+    """The free values of a goal search: the current joint 7, then the n - 1 midpoints
+    lo7 + (i + 0.5) / (n - 1) * (hi7 - lo7) of joint 7's range."""
+    n = int(n)
+    if n < 1:
+        raise ValueError("n must be at least 1")
+    lo7, hi7 = float(JOINT_LOWER[6]), float(JOINT_UPPER[6])
+    return np.array([float(current_q7)] +
+                    [lo7 + (i + 0.5) / (n - 1) * (hi7 - lo7) for i in range(n - 1)])
+
+
+def goal_search_for_pose(problem, start_conf, pose, torque_test, n_free=256, engine=None):
+    """The goal step of planner_fn_force_aware by search instead of by draw: every IK candidate
+    of the top grasp's gripper pose over free_grid(start_conf[6], n_free) through the joint
+    limits, torque_test's static test and the scene (Engine.goal_search), and of the feasible
+    ones the nearest to start_conf.  Returns (conf tuple or None, GoalStats).  Draws nothing
+    from np.random or random."""
+    from ._lib import engine as get_engine
+    from .scene import mesh_pack, obstacle_array
+
+    eng = get_engine() if engine is None else engine
+    eng.set_scene(obstacle_array(problem.fixed), mesh_pack(problem.fixed))
+    grasp = get_top_grasp(problem.payload)
+    gripper_pose = multiply(from_matrix(to_matrix(pose)), invert(grasp.value))
+    base_from_ee = get_base_from_ee(gripper_pose)
+    current = np.asarray(start_conf, dtype=np.float64)
+    q, _, _, _, stats = eng.goal_search(base_from_ee[None], free_grid(current[6], n_free), current,
+                                        torque_test.mode, torque_test.resolved_mass(None),
+                                        max_out=1)
+    if stats[0].n_out < 1:
+        return None, stats[0]
+    return tuple(float(v) for v in q[0, 0]), stats[0]

@@ -178,7 +178,16 @@ def planner_fn_force_aware(start_conf, pose, problem):
     from .ik import body_collision
     from .scene import mesh_pack, obstacle_array
     eng = get_engine()
-    grasp_conf = grasp_conf_for_pose(problem, start_conf, pose, engine=eng)
+    gs = getattr(problem, "goal_search", False)
+    if gs:
+        # opt-in: the nearest candidate that passes limits, torque test and scene, or None when
+        # the grid holds none; the reference's own checks below then pass by construction
+        from .ik import goal_search_for_pose
+        kw = {} if gs is True else {"n_free": int(gs)}
+        grasp_conf, _ = goal_search_for_pose(problem, start_conf, pose, torque_test, engine=eng,
+                                             **kw)
+    else:
+        grasp_conf = grasp_conf_for_pose(problem, start_conf, pose, engine=eng)
     # any(pairwise_collision(robot, b) for b in obstacles) (:260): body level, link0 included
     eng.set_scene(obstacle_array(obstacles), mesh_pack(obstacles))
     if grasp_conf is None or body_collision(eng, grasp_conf):

@@ -38,10 +38,13 @@ class Problem:
     final torque validation instead of dropping it (rrt_star_force_aware(retime=True));
     retime="runs": per run between the waypoints at rest (rrt_star_force_aware(retime="runs")).
     repair (no reference counterpart): planner_fn_force_aware collision-checks the min-jerk rows
-    and puts colliding segments back on their chords (rrt_star_force_aware(repair=True))."""
+    and puts colliding segments back on their chords (rrt_star_force_aware(repair=True)).
+    goal_search (no reference counterpart): planner_fn_force_aware picks the goal configuration
+    by ik.goal_search_for_pose (every IK candidate through limits, torque test and scene, the
+    nearest feasible one) instead of the reference's random draw; an int gives n_free."""
 
     def __init__(self, robot, fixed, payload, payload_mass, execution_time, torque_test="arne",
-                 *, repair=False, retime=False):
+                 *, goal_search=False, repair=False, retime=False):
         self.robot = robot
         self.fixed = fixed
         self.payload = payload
@@ -50,6 +53,7 @@ class Problem:
         self.torque_test = torque_test
         self.retime = retime
         self.repair = repair
+        self.goal_search = goal_search
 
 
 def get_arm_joints(robot, arm=None):
