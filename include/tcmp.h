@@ -667,7 +667,12 @@ int tcmp_plan_debug_round(tcmp_handle* h, int64_t cap, double* cand, int32_t* nn
  * (panda_primitives.py:240-265); tcmp_ik replays that.  tcmp_goal_search evaluates EVERY
  * candidate instead.  Candidate id = f * 8 + k of pose p is slot k of
  * tcmp_ik(poses[p], free_q7[f]), k < that call's count, and its configuration is tcmp_ik's bit
- * for bit (the same kernel runs).  Filters, in order:
+ * for bit (the same kernel runs), with one exception: tcmp_ik reports angles in (-pi, pi] and
+ * joint 6's range reaches 3.7525, so a candidate whose q6 is below the lower limit while
+ * q6 + 2 pi is at most the upper limit is taken at q6 + 2 pi (the only image that can be inside:
+ * q6 <= -2.5307 never is), and the filters, the distance and q_out all use that image.  tcmp_ik
+ * itself and the replay of the reference's choice keep the reported angle, as the reference does.
+ * Filters, in order:
  *   limits     every joint within the limits, inclusive (collision_fn's test);
  *   torque     the six tested torques as the mode's test sees them at rest (zero rates): the
  *              candidate passes iff every !(|t_j| >= L_j), tcmp_torque_ok's comparison (a NaN

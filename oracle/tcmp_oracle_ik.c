@@ -14,7 +14,9 @@
  * (rne.py:32-63, golden tests/golden/fk_golden.npz) and every IK solution must map back
  * through it to the requested pose; the ikfast solution ORDER is not reproduced (the
  * reference shuffles it anyway, ikfast.py:163 randomize).  Written with explicit DH matrices
- * and 3x3 products; the HIP version (csrc/tcmp_ik.h) is expanded by hand.
+ * and 3x3 products; the HIP version (csrc/tcmp_ik.h) is expanded by hand.  Both follow one
+ * contract at the folds and the shoulder singularity, pinned against a 50-digit
+ * restatement by tests/test_ik_edges_host.py and tests/test_gpu_ik_edges.py.
  */
 #include <math.h>
 #include <string.h>
@@ -64,6 +66,12 @@ ORC_API void orc_fk8(const double* q, double* R9, double* p3) {
   }
 }
 
+/* acceptance band of the two fold tests: the reference's solver takes |sin|, |cos| up to
+ * 1 + IKFAST_SINCOS_THRESH = 1e-7 and clamps (ikfast_panda_arm.cpp:110) */
+#define IK_BAND 1e-7
+/* below this sin|q2| joint 1 has no direction of its own */
+#define IK_SHOULDER 1e-12
+
 static double wrap_pi(double a) {
   while (a > M_PI) a -= 2 * M_PI;
   while (a <= -M_PI) a += 2 * M_PI;
@@ -94,8 +102,10 @@ ORC_API int orc_ik8(const double* R9, const double* p3, double q7, double* sols,
   const double C4 = (L2 - K0) / r4;
   int n = 0;
   for (int k = 0; k < 8; ++k) valid[k] = 0;
-  if (!(fabs(C4) <= 1.0)) return 0;
-  const double acos4 = atan2(sqrt(1.0 - C4 * C4), C4);
+  /* a fold quantity up to 1 + IK_BAND is the fold itself, rounded: clamp it */
+  if (!(fabs(C4) <= 1.0 + IK_BAND)) return 0;
+  const double C4c = fmin(1.0, fmax(-1.0, C4));
+  const double acos4 = atan2(sqrt(1.0 - C4c * C4c), C4c);
   /* u in frame 6 */
   double u6[3];
   for (int k = 0; k < 3; ++k) u6[k] = R6[0][k] * u[0] + R6[1][k] * u[1] + R6[2][k] * u[2];
@@ -106,8 +116,8 @@ ORC_API int orc_ik8(const double* R9, const double* p3, double q7, double* sols,
     /* z5 . (O2 - O5) and the in-plane length (frame-5 chain) */
     const double K = -b + a * s4 - d * c4;
     const double W = a - a * c4 - d * s4;
-    if (!(r6 > 0) || !(fabs(K / r6) <= 1.0)) continue;
-    const double S6 = K / r6, as6 = atan2(S6, sqrt(1.0 - S6 * S6));
+    if (!(r6 > 0) || !(fabs(K / r6) <= 1.0 + IK_BAND)) continue;
+    const double S6 = fmin(1.0, fmax(-1.0, K / r6)), as6 = atan2(S6, sqrt(1.0 - S6 * S6));
     for (int i6 = 0; i6 < 2; ++i6) {
       const double q6 = wrap_pi(i6 ? (M_PI - as6 - beta) : (as6 - beta));
       double R56[3][3], t56[3], R5[3][3], u5[3];
@@ -126,14 +136,16 @@ ORC_API int orc_ik8(const double* R9, const double* p3, double q7, double* sols,
       for (int i2 = 0; i2 < 2; ++i2) {
         const double sgn = i2 ? -1.0 : 1.0;
         const double q2 = atan2(sgn * sb, R3[2][2]);
-        double q1, q3;
-        if (sb > 1e-12) {
-          q1 = atan2(sgn * R3[1][2], sgn * R3[0][2]);
-          q3 = atan2(sgn * R3[2][1], -sgn * R3[2][0]);
-        } else { /* wrist-1 singular: q1 + q3 (or q1 - q3) fixed; take q1 = 0 */
-          q1 = 0.0;
-          q3 = atan2(R3[1][0], R3[0][0]) * (R3[2][2] > 0 ? 1.0 : -1.0);
+        /* q1 from z3's direction, or 0 where it has none (shoulder singular: only the sum
+         * is fixed); q3 from Rz(-q1) R3 = Ry(q2) Rz(q3), whose row 1 is (s3, c3, 0) for every
+         * q2, so q3 absorbs whatever error q1 carries near the singularity */
+        double c1 = 1.0, s1 = 0.0;
+        if (sb > IK_SHOULDER) {
+          c1 = sgn * R3[0][2] / sb;
+          s1 = sgn * R3[1][2] / sb;
         }
+        const double q1 = sb > IK_SHOULDER ? atan2(s1, c1) : 0.0;
+        const double q3 = atan2(c1 * R3[1][0] - s1 * R3[0][0], c1 * R3[1][1] - s1 * R3[0][1]);
         const int slot = 4 * i4 + 2 * i6 + i2;
         double* o = sols + 7 * slot;
         o[0] = q1; o[1] = q2; o[2] = q3; o[3] = q4; o[4] = q5; o[5] = q6; o[6] = q7;

@@ -6,12 +6,17 @@
 // pose is evaluated instead: candidate id = f * 8 + k of pose p is slot k of
 // tcmp_ik(poses[p], free_q7[f]), filtered by the joint limits, the mode's torque test at rest and
 // the scene's collision check, and the feasible ones come back ordered by (distance from ref, id).
+// tcmp_ik reports angles in (-pi, pi] and joint 6's range reaches 3.7525: a candidate whose q6 is
+// below the lower limit while q6 + 2 pi is at most the upper one is taken at that image (it is
+// the only one: q6 <= -2.5307 is never inside itself), so ids keep their meaning; the limits, the
+// distance, the torque and collision tests and the returned configuration all use the image.
 //
 // Stages (one host wait, nothing persistent, no inter-workgroup waiting anywhere):
 //   k_goal_expand   the (pose, free value) rows k_ik takes, one lane each
 //   k_ik            as compiled (tcmp_ik.h): the candidates are tcmp_ik's bit for bit
 //   k_goal_base     panda_link0's depths (launch_base_pd) to one flag
-//   k_goal_torque   one lane per slot: limits, torques at rest, verdict, headroom, distance; the
+//   k_goal_torque   one lane per slot: joint 6's image (written back to the candidate), limits,
+//                   torques at rest, verdict, headroom, distance; the
 //                   poses' counters (integer atomics); survivors appended to a work list
 //   k_goal_collide  one survivor per lane through collides_wave; a hit clears the slot's key.
 //                   The grid covers every slot; blocks past the list's device-side length return
@@ -25,6 +30,7 @@
 namespace {
 
 constexpr unsigned long long kGoalNone = ~0ull;  // a slot's key while it is not feasible
+constexpr double kGoal2Pi = 6.283185307179586;
 
 // rows i = p * n_free + f of k_ik's inputs
 __global__ __launch_bounds__(256) void k_goal_expand(const double* __restrict__ poses,
@@ -55,7 +61,7 @@ __global__ void k_goal_base(const double* __restrict__ base_pd, int n_base,
 // (solutions, in limits, torque ok, [feasible: k_goal_select's]); ctl[0]: the work list's length.
 template <int MODE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE >= 2 ? 1 : 2)))
-void k_goal_torque(const double* __restrict__ sols, const int* __restrict__ count, int n_free,
+void k_goal_torque(double* __restrict__ sols, const int* __restrict__ count, int n_free,
                    long long n_slots, const double* __restrict__ refw, double mass,
                    unsigned long long* __restrict__ key, double* __restrict__ head,
                    int* __restrict__ list, unsigned long long* ctl, unsigned long long* ctr) {
@@ -71,6 +77,10 @@ void k_goal_torque(const double* __restrict__ sols, const int* __restrict__ coun
   if (has) {
 #pragma unroll
     for (int k = 0; k < 7; ++k) q[k] = sols[7 * sl + k];
+    if (q[5] < kLo[5] && q[5] + kGoal2Pi <= kHi[5]) {  // joint 6's image above pi
+      q[5] += kGoal2Pi;
+      sols[7 * sl + 5] = q[5];
+    }
     lim = !limits_violated(q);
   }
   if (lim) {

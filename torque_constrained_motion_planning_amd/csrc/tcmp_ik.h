@@ -9,8 +9,19 @@
 // R_0^3 = Rz(q1) Ry(q2) Rz(q3) gives q1..q3 (two signs of q2).  Branch b = 4*i4 + 2*i6 + i2.
 // All angles come back in (-pi, pi] like ikfast's (e.g. :470-483); the limit filter is the
 // caller's (ikfast.py:166).  One lane per (pose, free value).
+//
+// Contract at the edges (tests/golden/gen_ik_edges.py restates it at 50 digits): the
+// two fold quantities, cos(q4 + phi) and sin(q6 + beta), are accepted up to 1 + kIkBand and
+// clamped, so the roots at full extension and at q5 = +-pi/2 are not lost to rounding (both
+// merging branches are emitted); where sin|q2| <= kIkShoulder joint 1 is 0 and q3 carries q1 + q3.
 #pragma once
 // Included by tcmp_engine.hip inside its kernel namespace.
+
+// acceptance band of the two fold tests: the reference's solver takes |sin|, |cos| up to
+// 1 + IKFAST_SINCOS_THRESH = 1e-7 and clamps (ikfast_panda_arm.cpp:110)
+constexpr double kIkBand = 1e-7;
+// below this sin|q2| joint 1 has no direction of its own
+constexpr double kIkShoulder = 1e-12;
 
 __device__ __forceinline__ double wrap_pi(double a) {
   constexpr double kPi = 3.141592653589793, k2Pi = 6.283185307179586;
@@ -62,8 +73,10 @@ __device__ __forceinline__ int ik8(const double R[9], const double p[3], double 
   const double r4 = hypot(K1, K2), phi = atan2(K2, K1);
   const double C4 = (L2 - K0) / r4;
   int c = 0;
-  if (!(fabs(C4) <= 1.0)) return 0;
-  const double acos4 = atan2(sqrt(1.0 - C4 * C4), C4);
+  // a fold quantity up to 1 + kIkBand is the fold itself, rounded: clamp it
+  if (!(fabs(C4) <= 1.0 + kIkBand)) return 0;
+  const double C4c = fmin(1.0, fmax(-1.0, C4));
+  const double acos4 = atan2(sqrt(1.0 - C4c * C4c), C4c);
   const double u6x = x6[0] * u[0] + x6[1] * u[1] + x6[2] * u[2];
   const double u6y = y6[0] * u[0] + y6[1] * u[1] + y6[2] * u[2];
   const double u6z = z6[0] * u[0] + z6[1] * u[1] + z6[2] * u[2];
@@ -74,8 +87,8 @@ __device__ __forceinline__ int ik8(const double R[9], const double p[3], double 
     sincos(q4, &s4, &c4);
     const double K = -b + a * s4 - d * c4;  // z5 . (O2 - O5)
     const double W = a - a * c4 - d * s4;   // in-plane length, sign fixes q5
-    if (!(r6 > 0.0) || !(fabs(K / r6) <= 1.0)) continue;
-    const double S6 = K / r6, as6 = atan2(S6, sqrt(1.0 - S6 * S6));
+    if (!(r6 > 0.0) || !(fabs(K / r6) <= 1.0 + kIkBand)) continue;
+    const double S6 = fmin(1.0, fmax(-1.0, K / r6)), as6 = atan2(S6, sqrt(1.0 - S6 * S6));
     for (int i6 = 0; i6 < 2; ++i6) {
       const double q6 = wrap_pi(i6 ? (kPi - as6 - beta) : (as6 - beta));
       double s6, c6;
@@ -116,14 +129,16 @@ __device__ __forceinline__ int ik8(const double R[9], const double p[3], double 
       for (int i2 = 0; i2 < 2; ++i2) {
         const double sgn = i2 ? -1.0 : 1.0;
         const double q2 = atan2(sgn * sb, z3[2]);
-        double q1, q3;
-        if (sb > 1e-12) {
-          q1 = atan2(sgn * z3[1], sgn * z3[0]);
-          q3 = atan2(sgn * y3[2], -sgn * x3[2]);
-        } else {  // q2 = 0 / pi: only q1 +- q3 is fixed; take q1 = 0
-          q1 = 0.0;
-          q3 = atan2(x3[1], x3[0]) * (z3[2] > 0.0 ? 1.0 : -1.0);
+        // q1 from z3's direction, or 0 where it has none (shoulder singular: only the sum is
+        // fixed); q3 from Rz(-q1) R3 = Ry(q2) Rz(q3), whose row 1 is (s3, c3, 0) for every q2,
+        // so q3 absorbs whatever error q1 carries near the singularity
+        double c1 = 1.0, s1 = 0.0;
+        if (sb > kIkShoulder) {
+          c1 = sgn * z3[0] / sb;
+          s1 = sgn * z3[1] / sb;
         }
+        const double q1 = sb > kIkShoulder ? atan2(s1, c1) : 0.0;
+        const double q3 = atan2(c1 * x3[1] - s1 * x3[0], c1 * y3[1] - s1 * y3[0]);
         double* o = out + 7 * c++;
         o[0] = q1; o[1] = q2; o[2] = q3; o[3] = q4;
         o[4] = q5; o[5] = q6; o[6] = q7;
