@@ -636,6 +636,100 @@ int tcmp_retime_runs_traj(tcmp_handle* h, const double* q, const double* qd, con
 int tcmp_plan_retime_runs(tcmp_handle* h, const tcmp_retime_cfg* cfg, tcmp_retime_run* runs,
                           int64_t cap_runs, tcmp_retime_runs_result* res);
 
+/* Torque-limited velocity-profile retiming (no reference counterpart).  Both retimings above play
+ * the rows at a constant time scale, so the worst row sets the speed of its whole trajectory or
+ * run.  Let the scale vary along the path instead: with the path parameter the original time
+ * (psg), x = sd^2 and u = sdd, row (q, v, a) becomes (q, v sqrt(x), a x + v u) and its torque is
+ *   tau = g(q) + u m + x d,   g = T(q, 0, 0), m = T(q, 0, v) - g, d = T(q, v, a) - g
+ * (T: the six tested joints' torques as the mode's test sees them; the rates are read as
+ * derivatives with respect to psg), affine in (u, x): the constant-scale identity is its u = 0
+ * case.  The torque test of a row is 12 half-planes in (u, x), neighbouring rows are linked by
+ * x_{i+1} = x_i + 2 D_i u_i, and the fastest profile comes from a backward pass over the
+ * reachable sets and a forward greedy pass (time-optimal path parameterisation by reachability
+ * analysis, discretised at the rows).
+ * Per trajectory of rows i = 0 .. n-1: D_i = psg[i+1] - psg[i] > 0 (1 without psg),
+ * L = 87 87 87 87 12 12, eps = 1e-9, Lg = L - eps, x_max = 1 / min_scale^2.
+ * Coefficients: g, m, d from three passes of one instruction stream, so m = d = 0 exactly on a
+ * row at rest and in nov mode; base: no constraint.
+ * Uniform floor: x_u and the uniform status are tcmp_retime_traj's on these rows with the same
+ * cfg (ub / lb from g and d).  Uniform OK: x_floor = x_u and the trajectory is anchored; else
+ * x_floor = max_scale > 0 ? 1 / max_scale^2 : 1e-6, not anchored.
+ * Lines of row i, each p - s x <= u <= P - S x:
+ *   joint j, m_j != 0, A = |m_j|, sigma = sign(m_j):
+ *     (P, S) = ((Lg_j - sigma g_j) / A, sigma d_j / A), (p, s) = ((-Lg_j - sigma g_j) / A, S);
+ *   m_j == 0: the joint bounds x directly, by tcmp_retime_traj's ub / lb rules for d_j (d_j == 0
+ *     included); a NaN among g_j, m_j, d_j: ub = -inf, lb = +inf;
+ *   i < n-1, the link to row i+1's set: (P, S) = (hi_{i+1} / (2 D_i), 1 / (2 D_i)),
+ *     (p, s) = (lo_{i+1} / (2 D_i), 1 / (2 D_i)).
+ * Backward pass, i = n-1 .. 0 (u eliminated, so no vertex needs a tolerance): for every (upper k,
+ * lower j) pair, at most 7 x 7, c = S_k - s_j, e = P_k - p_j: c > 0: x <= e / c; c < 0:
+ * x >= e / c; c == 0 && e < 0: empty.  hi_i = min(x_max, direct ubs, pair ubs),
+ * lo_i = max(x_floor, direct lbs, pair lbs).  Anchored: lo_i = x_floor, hi_i = max(hi_i, x_floor)
+ * (the constant profile x_u lies in every set in exact arithmetic; only rounding can empty one,
+ * which the guard and the validation cover).  Not anchored: !(lo_i <= hi_i) gives INFEASIBLE with
+ * fail_row = i, the highest such row.
+ * Forward pass: x_0 = hi_0; U = min over the row's joint upper lines of P - S x_i (+inf without
+ * any), W = max over its joint lower lines (-inf); i < n-1: t = min(U, (hi_{i+1} - x_i) / (2 D_i)),
+ * x_{i+1} = min(hi_{i+1}, max(lo_{i+1}, x_i + 2 D_i t)), u_i = (x_{i+1} - x_i) / (2 D_i); the last
+ * row (and n = 1): u = min(U, max(0, W)).
+ * Time: r_i = sqrt(x_i); psg'_0 = psg_0, psg'_{i+1} = psg'_i + 2 D_i / (r_i + r_{i+1}), summed in
+ * row order; time_before = psg_{n-1} - psg_0, time_after = psg'_{n-1} - psg'_0, time_uniform the
+ * same sum with x = x_u everywhere (0 when not anchored).
+ * Rows: x_i == 1 && u_i == 0 copies the row; else qd' = qd r_i, qdd' = qdd x_i + qd u_i, each
+ * product rounded before the add; q is untouched (a repair's collision verdict stays valid).
+ * All of it fp64 without contraction.  The new rows go through the mode's ordinary torque test;
+ * a failing row gives UNVERIFIED and the outputs are left alone.  Deterministic.
+ * Consequences: a trajectory that passes at min_scale = 1 has x_u = 1 = x_max, so x = 1, u = 0 on
+ * every row and every bit is kept.  Anchored: x_i >= x_u on every row and
+ * time_after <= time_uniform, exactly -- never slower than tcmp_retime_traj.  Not anchored, it
+ * also times rows the uniform retiming calls INFEASIBLE (rows that need acceleration to stay
+ * inside a limit).  The acceleration is piecewise constant in the path parameter: the retimed
+ * motion is C^1 with bounded jumps of qdd at the rows, where tcmp_plan_retime_runs stays C^2.
+ * Velocity and jerk limits are not part of this. */
+typedef struct {
+  int32_t status;            /* TCMP_RETIME_OK / INFEASIBLE / UNVERIFIED (plan form: NOT_APPLICABLE) */
+  int32_t anchored;          /* the uniform retiming is OK and its x is the floor of every set */
+  int32_t uniform_status;    /* tcmp_retime_traj's status on these rows (OK / INFEASIBLE / OVER_CAP) */
+  int32_t pad;
+  int64_t n_rows;
+  int64_t fail_row;          /* INFEASIBLE: the highest row whose set is empty, else -1 */
+  int64_t first_fail_before; /* the validation's first failing row as given, -1 = none */
+  int64_t first_fail_after;  /* of the new rows (OK: -1); first_fail_before when not written */
+  int64_t n_at_floor, n_at_cap; /* rows with x_i == x_floor, x_i == x_max */
+  double x_uniform;          /* tcmp_retime_traj's x; 0 unless uniform_status is OK */
+  double x_floor;
+  double x_min;              /* min x_i (n = 0: x_max); 0 when INFEASIBLE */
+  double time_before, time_after, time_uniform; /* after, uniform: 0 when INFEASIBLE */
+  double exec_time_after;    /* tcmp_plan_retime_profile; else 0 */
+  double ms;                 /* device time of the whole call (0 with timing off) */
+} tcmp_retime_profile_result; /* rows (fail_row, first_fail_*) count from the trajectory's start */
+
+/* retime n_traj independent trajectories stored back to back: traj_off holds n_traj + 1 ascending
+ * offsets from 0, trajectory t is rows [traj_off[t], traj_off[t+1]) of q, qd, qdd (n x 7,
+ * n = traj_off[n_traj]) and psg (n, or NULL; strictly ascending inside a trajectory, status -1
+ * otherwise).  qd_out, qdd_out (n x 7), psg_out (n, NULL iff psg is), x_out and u_out (n each, or
+ * NULL) are written for the trajectories whose status is OK and left alone for the others;
+ * coef_out (n x 18: g, m, d per row as the device computed them; debug; or NULL) is always
+ * written.  results: n_traj records.  An empty trajectory gives OK.  ms (or NULL): the device
+ * time of the call.  cfg NULL = {1, 0}.  One wavefront sweeps one trajectory, so the call is
+ * sized for many trajectories of up to thousands of rows.  Leaves an open plan alone. */
+int tcmp_retime_profile_traj(tcmp_handle* h, const double* q, const double* qd, const double* qdd,
+                             const double* psg, const int64_t* traj_off, int64_t n_traj,
+                             int32_t torque_mode, double payload_mass, const tcmp_retime_cfg* cfg,
+                             double* qd_out, double* qdd_out, double* psg_out, double* x_out,
+                             double* u_out, double* coef_out, tcmp_retime_profile_result* results,
+                             double* ms);
+
+/* velocity-profile retiming of the open plan's last trajectory finish.  Applies exactly when
+ * tcmp_plan_retime does; otherwise res->status is TCMP_RETIME_NOT_APPLICABLE and nothing changes.
+ * On OK it acts as tcmp_plan_retime does: the engine's qd, qdd and psg rows are the new ones, tau
+ * is recomputed, the stored status is TCMP_PLAN_OK with first_fail -1,
+ * exec_time_after = execution_time * time_after / time_before (execution_time when time_before
+ * is 0), and every retiming form and tcmp_plan_repair are NOT_APPLICABLE until the next finish.
+ * Any other status leaves every row as it was. */
+int tcmp_plan_retime_profile(tcmp_handle* h, const tcmp_retime_cfg* cfg,
+                             tcmp_retime_profile_result* res);
+
 /* copy the finished plan: waypoints (n_waypoints x 7), trajectory q/qd/qdd (n_traj x 7),
  * psg (n_traj), tau = Conf.torques without payload (n_traj x 7).  Any pointer may be NULL. */
 int tcmp_plan_fetch(tcmp_handle* h, double* waypoints, double* q, double* qd, double* qdd,

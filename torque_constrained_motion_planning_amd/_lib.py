@@ -40,6 +40,7 @@ EXPORTS = [
     "tcmp_retime_traj", "tcmp_plan_retime",
     "tcmp_repair_traj", "tcmp_plan_repair",
     "tcmp_minjerk_runs", "tcmp_retime_runs_traj", "tcmp_plan_retime_runs",
+    "tcmp_retime_profile_traj", "tcmp_plan_retime_profile",
     "tcmp_tier0_tables", "tcmp_tier0_masks",
     "tcmp_debug_pair_pd", "tcmp_gauss_clusters", "tcmp_debug_wave_reduce",
     "tcmp_goal_search",
@@ -165,6 +166,24 @@ class RetimeRunsResult(ctypes.Structure):
         ("first_fail_before", ctypes.c_int64), ("first_fail_after", ctypes.c_int64),
         ("x_min", ctypes.c_double), ("time_ratio", ctypes.c_double),
         ("exec_time_after", ctypes.c_double), ("ms", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+class RetimeProfileResult(ctypes.Structure):
+    """tcmp_retime_profile_result"""
+    _fields_ = [
+        ("status", ctypes.c_int32), ("anchored", ctypes.c_int32),
+        ("uniform_status", ctypes.c_int32), ("pad", ctypes.c_int32),
+        ("n_rows", ctypes.c_int64), ("fail_row", ctypes.c_int64),
+        ("first_fail_before", ctypes.c_int64), ("first_fail_after", ctypes.c_int64),
+        ("n_at_floor", ctypes.c_int64), ("n_at_cap", ctypes.c_int64),
+        ("x_uniform", ctypes.c_double), ("x_floor", ctypes.c_double), ("x_min", ctypes.c_double),
+        ("time_before", ctypes.c_double), ("time_after", ctypes.c_double),
+        ("time_uniform", ctypes.c_double), ("exec_time_after", ctypes.c_double),
+        ("ms", ctypes.c_double),
     ]
 
     def as_dict(self):
@@ -321,6 +340,13 @@ def load_library(path=LIB_PATH):
             L.tcmp_plan_retime_runs.argtypes = [vp, ctypes.POINTER(RetimeCfg),
                                                 ctypes.POINTER(RetimeRun), ctypes.c_int64,
                                                 ctypes.POINTER(RetimeRunsResult)]
+        if hasattr(L, "tcmp_retime_profile_traj"):  # absent from A/B builds of older sources
+            L.tcmp_retime_profile_traj.argtypes = [
+                vp, _dp, _dp, _dp, _dp, _i64p, ctypes.c_int64, ctypes.c_int32, ctypes.c_double,
+                ctypes.POINTER(RetimeCfg), _dp, _dp, _dp, _dp, _dp, _dp,
+                ctypes.POINTER(RetimeProfileResult), _dp]
+            L.tcmp_plan_retime_profile.argtypes = [vp, ctypes.POINTER(RetimeCfg),
+                                                   ctypes.POINTER(RetimeProfileResult)]
         if hasattr(L, "tcmp_tier0_tables"):  # absent from A/B builds of older sources
             _f32p, _u32p = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_uint32)
             L.tcmp_tier0_tables.argtypes = [_dp, ctypes.c_int32, ctypes.c_int32, _f32p, _u32p, _f32p]
@@ -727,6 +753,56 @@ class Engine:
                 continue
             self._check(rc)
             return list(runs[:r.n_runs]), r
+
+    def retime_profile(self, q, qd, qdd, mode, mass, psg=None, traj_off=None, min_scale=1.0,
+                       max_scale=0.0, want_coef=False):
+        """tcmp_retime_profile_traj: the fastest time scale that varies along the path, x = sd^2
+        and u = sdd per row, under which rows (q, qd sqrt(x), qdd x + qd u) pass the torque test
+        of `mode`; never slower than retime() where that one is feasible.  traj_off: n_traj + 1
+        ascending row offsets of independent trajectories stored back to back (None: one) ->
+        dict(qd, qdd, psg | None, x, u, results=[RetimeProfileResult], ms[, coef (n, 18)]).
+        A trajectory's rows come back retimed when its status is RETIME_OK and as given
+        otherwise (x = 1, u = 0 there)."""
+        if not hasattr(self.L, "tcmp_retime_profile_traj"):
+            raise TcmpError("tcmp_retime_profile_traj: not in this library build")
+        q = _rows(q, "q"); qd = _rows(qd, "qd"); qdd = _rows(qdd, "qdd")
+        if not len(q) == len(qd) == len(qdd):
+            raise ValueError("q, qd and qdd must have the same number of rows")
+        if psg is not None:
+            psg = np.ascontiguousarray(np.asarray(psg, dtype=np.float64).reshape(-1))
+            if len(psg) != len(q):
+                raise ValueError("one psg value per row")
+        off = np.ascontiguousarray(np.asarray([0, len(q)] if traj_off is None else traj_off,
+                                              dtype=np.int64).reshape(-1))
+        if len(off) < 1 or off[-1] != len(q):
+            raise ValueError("traj_off must end at the number of rows")
+        n_traj = len(off) - 1
+        cfg = RetimeCfg(float(min_scale), float(max_scale))
+        res = (RetimeProfileResult * max(n_traj, 1))()
+        ms = ctypes.c_double(0.0)
+        oqd = qd.copy(); oqdd = qdd.copy()
+        opsg = None if psg is None else psg.copy()
+        x = np.ones(len(q)); u = np.zeros(len(q))
+        coef = np.zeros((len(q), 18)) if want_coef else None
+        self._check(self.L.tcmp_retime_profile_traj(
+            self.h, _d(q), _d(qd), _d(qdd), _d(psg), off.ctypes.data_as(_i64p), n_traj, int(mode),
+            float(mass), ctypes.byref(cfg), _d(oqd), _d(oqdd), _d(opsg), _d(x), _d(u), _d(coef),
+            res, ctypes.byref(ms)))
+        out = dict(qd=oqd, qdd=oqdd, psg=opsg, x=x, u=u, results=list(res[:n_traj]), ms=ms.value)
+        if want_coef:
+            out["coef"] = coef
+        return out
+
+    def plan_retime_profile(self, min_scale=1.0, max_scale=0.0):
+        """tcmp_plan_retime_profile: velocity-profile retiming of the rows of the open plan's
+        last plan_finish -> RetimeProfileResult; on RETIME_OK plan_fetch returns the retimed
+        trajectory."""
+        if not hasattr(self.L, "tcmp_plan_retime_profile"):
+            raise TcmpError("tcmp_plan_retime_profile: not in this library build")
+        cfg = RetimeCfg(float(min_scale), float(max_scale))
+        r = RetimeProfileResult()
+        self._check(self.L.tcmp_plan_retime_profile(self.h, ctypes.byref(cfg), ctypes.byref(r)))
+        return r
 
     def repair_traj(self, waypoints, ni, check_only=False, max_passes=0):
         """tcmp_repair_traj: the min-jerk rows of `waypoints` (n, 7), ni per segment, with the

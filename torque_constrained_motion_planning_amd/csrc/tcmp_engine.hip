@@ -1549,6 +1549,16 @@ struct tcmp_handle {
   DBuf<long long> rr_off;
   DBuf<double> rr_org;
   std::vector<unsigned char> rr_host;
+  // velocity-profile retiming (tcmp_retime_profile.h): the three torque passes' rows of 6, the
+  // rows' 18 coefficients and as-given verdicts, the reachable sets, the profile (x, u), the
+  // trajectories' offsets, records and first failing rows, and the host side of the outputs
+  DBuf<double> pf_t[3], pf_coef, pf_hi, pf_lo, pf_x, pf_u;
+  DBuf<int> pf_bad;
+  DBuf<long long> pf_off;
+  DBuf<unsigned long long> pf_ff;
+  DBuf<unsigned char> pf_res;
+  std::vector<unsigned char> pf_host;
+  std::vector<long long> pf_hoff;
   // goal search (tcmp_goal.h): the poses, free values and (ref, weights) as given, their
   // per-(pose, free value) expansion for k_ik, its solutions and counts, the slots' keys
   // (distance bits, all ones: not feasible) and headrooms, the torque stage's work list, the
@@ -2243,6 +2253,13 @@ int tcmp_destroy(tcmp_handle* h) {
   for (auto* b : {&h->rr_rows, &h->rr_part, &h->rr_tab}) b->release();
   h->rr_off.release();
   h->rr_org.release();
+  for (auto* b : {&h->pf_t[0], &h->pf_t[1], &h->pf_t[2], &h->pf_coef, &h->pf_hi, &h->pf_lo, &h->pf_x,
+                  &h->pf_u})
+    b->release();
+  h->pf_bad.release();
+  h->pf_off.release();
+  h->pf_ff.release();
+  h->pf_res.release();
   for (auto* b : {&h->gs_pose, &h->gs_free, &h->gs_refw, &h->gs_xpose, &h->gs_xfree, &h->gs_sol,
                   &h->gs_head, &h->gs_out})
     b->release();
@@ -4354,4 +4371,5 @@ int tcmp_plan_debug_round(tcmp_handle* h, int64_t cap, double* cand, int32_t* nn
 #include "tcmp_retime.h"
 #include "tcmp_repair.h"
 #include "tcmp_retime_runs.h"
+#include "tcmp_retime_profile.h"
 #include "tcmp_goal.h"

@@ -69,6 +69,11 @@ def rrt_star_force_aware(start, goal, distance, sample, extend, collision, torqu
     continuous piecewise-linear warp (Engine.plan_retime_runs); engine loop with the package's
     own dynamics fn only (a foreign dynam_fn's rows have no waypoints or gates to derive runs
     from: ValueError).
+    retime="profile": the time scale varies along the path instead -- the fastest velocity
+    profile whose rows pass the torque test, which slows down only where a torque binds and is
+    never slower than retime=True where that is feasible (Engine.plan_retime_profile, or
+    Engine.retime_profile on a foreign dynam_fn's rows with their psg).  The retimed motion is
+    C^1: the accelerations jump at the rows.
     repair (no reference counterpart, off by default): the min-jerk rows are checked against
     collision_fn on the device and the segments whose rows collide are put back on their
     checked chords (Engine.plan_repair) before the validation's verdict is used and before any
@@ -122,14 +127,16 @@ def rrt_star_force_aware(start, goal, distance, sample, extend, collision, torqu
 
 def _retime_kw(retime, **kw):
     """The retime argument of the drop-ins -> _finish's: None (off), or the keywords of the
-    stage, with runs=True for the per-run form."""
+    stage, with runs=True for the per-run form and profile=True for the velocity profile."""
     if retime is False or retime is None:
         return None
     if retime is True:
         return dict(kw)
     if retime == "runs":
         return dict(kw, runs=True)
-    raise ValueError('retime must be False, True or "runs" (got %r)' % (retime,))
+    if retime == "profile":
+        return dict(kw, profile=True)
+    raise ValueError('retime must be False, True, "runs" or "profile" (got %r)' % (retime,))
 
 
 # ---- shared tail: dynam_fn + final validation (rrt_star.py:202-211) --------------------------
@@ -145,6 +152,14 @@ def _validate_and_return(rrt_path, dynam_fn, torque_fn, native_torque, retime=Fa
                                                np.asarray(accels, dtype=np.float64)[:, :7],
                                                torque_fn.mode, torque_fn.payload_mass,
                                                want_tau=False)
+        if first_fail >= 0 and retime == "profile":
+            o = _lib.engine().retime_profile(q, np.asarray(vels, dtype=np.float64)[:, :7],
+                                             np.asarray(accels, dtype=np.float64)[:, :7],
+                                             torque_fn.mode, torque_fn.payload_mass, psg=psg)
+            if o["results"][0].status != _lib.RETIME_OK:
+                return None, None, None, None
+            return (path, [list(x) for x in o["qd"]], [list(x) for x in o["qdd"]],
+                    [float(x) for x in o["psg"]])
         if first_fail >= 0 and retime:
             v, a, p, rt = _lib.engine().retime(q, np.asarray(vels, dtype=np.float64)[:, :7],
                                                np.asarray(accels, dtype=np.float64)[:, :7],
@@ -169,15 +184,18 @@ def _finish(eng, dynam_fn=None, torque_fn=None, retime=None, repair=None):
     is retimed and fetched again, and out["retime"] is the RetimeResult (None when the stage did
     not run); a foreign dynam_fn's rows go through Engine.retime instead.  With runs=True among
     them the stage is Engine.plan_retime_runs: out["retime"] is the RetimeRunsResult and
-    out["retime_runs"] the per-run table.
+    out["retime_runs"] the per-run table.  With profile=True the stage is
+    Engine.plan_retime_profile (out["retime"] is the RetimeProfileResult), and a foreign
+    dynam_fn's rows go through Engine.retime_profile with their psg.
     repair: None, or the keywords of Engine.plan_repair, run between the finish and the retiming:
     out["repair"] is the RepairResult; rows it replaced are fetched again with the new
     validation's verdict, and a trajectory it could not clear is dropped like one that fails the
     validation."""
-    by_runs = False
+    by_runs = by_profile = False
     if retime is not None:
         retime = dict(retime)
         by_runs = bool(retime.pop("runs", False))
+        by_profile = bool(retime.pop("profile", False))
     if by_runs and dynam_fn is not None:
         raise ValueError('retime="runs" needs the engine\'s own min-jerk (no waypoints or gates '
                          "to derive runs from)")
@@ -189,7 +207,7 @@ def _finish(eng, dynam_fn=None, torque_fn=None, retime=None, repair=None):
         out = eng.plan_fetch(r)
         rrt_path = [tuple(x) for x in out["waypoints"]]
         return _validate_and_return(rrt_path, dynam_fn, torque_fn, True,
-                                    retime is not None), r, out
+                                    "profile" if by_profile else retime is not None), r, out
     print("run min jerk")
     if r.status == _lib.PLAN_MINJERK_ASSERT:
         raise AssertionError("Invalid number of intervals chosen (must be greater than 0)")
@@ -209,6 +227,8 @@ def _finish(eng, dynam_fn=None, torque_fn=None, retime=None, repair=None):
         if r.status == _lib.PLAN_VALIDATION_FAILED:
             if by_runs:
                 out["retime_runs"], out["retime"] = eng.plan_retime_runs(**retime)
+            elif by_profile:
+                out["retime"] = eng.plan_retime_profile(**retime)
             else:
                 out["retime"] = eng.plan_retime(**retime)
             if out["retime"].status == _lib.RETIME_OK:
@@ -279,6 +299,8 @@ def rrt_star_batched(start, goal, obstacles, torque_mode, payload_mass, executio
     retimed rows with status 0; raw["retime"] is the RetimeResult (None when the stage did not
     run).  retime="runs": per run between the waypoints at rest (Engine.plan_retime_runs);
     raw["retime"] is the RetimeRunsResult and raw["retime_runs"] the per-run table.
+    retime="profile": the fastest velocity profile along the path (Engine.plan_retime_profile);
+    raw["retime"] is the RetimeProfileResult.
     repair: after the finish and before any retiming, collision repair of the min-jerk rows
     (Engine.plan_repair); raw["repair"] is the RepairResult, and a trajectory that still
     collides comes back as (None,)*4.

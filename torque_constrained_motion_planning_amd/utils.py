@@ -36,7 +36,9 @@ class Problem:
     """utils.py:86-93, verbatim fields.  robot: PandaRobot; fixed: [Box]; payload: Payload.
     retime (no reference counterpart): planner_fn_force_aware retimes a trajectory that fails the
     final torque validation instead of dropping it (rrt_star_force_aware(retime=True));
-    retime="runs": per run between the waypoints at rest (rrt_star_force_aware(retime="runs")).
+    retime="runs": per run between the waypoints at rest (rrt_star_force_aware(retime="runs"));
+    retime="profile": a time scale that varies along the path, slowing down only where a torque
+    binds (rrt_star_force_aware(retime="profile")).
     repair (no reference counterpart): planner_fn_force_aware collision-checks the min-jerk rows
     and puts colliding segments back on their chords (rrt_star_force_aware(repair=True)).
     goal_search (no reference counterpart): planner_fn_force_aware picks the goal configuration
