@@ -28,7 +28,7 @@ def coefficients(q, v, a, mode, mass):
 
 def joint_bounds(g, d):
     """The uniform retiming's ub / lb of every (row, joint) from g and d = tau - g (tcmp.h;
-    csrc/tcmp_retime.h k_rt_bounds)."""
+    csrc/tcmp_stage.h rt_interval)."""
     g, d = np.asarray(g, dtype=np.float64), np.asarray(d, dtype=np.float64)
     L = np.broadcast_to(LIMITS, g.shape)
     inside = np.abs(g) < L

@@ -398,8 +398,8 @@ F_SAMPLES, F_BATCH, F_SEED, F_EXEC, F_MODE, F_MASS = 2048, 64, 129, 5.0, 3, 5.0
 
 
 def test_repair_of_a_plan_that_fails_validation_then_retime(eng):
-    """Repair closes gates on a status-3 plan, the new validation flags a row (k_rp_validate,
-    k_rp_commit store status 3 and that row), the retiming that follows works on the repaired
+    """Repair closes gates on a status-3 plan, the new validation flags a row (k_validate,
+    k_stage_commit store status 3 and that row), the retiming that follows works on the repaired
     rows, and the final rows pass the validation and collide nowhere; the drop-in runs the same
     chain."""
     import retime_ref as RT

@@ -404,6 +404,18 @@ def _rows(x, name="array"):
     return a.reshape(-1, 7)
 
 
+def _traj_arrays(q, qd, qdd, psg):
+    """A trajectory's rows as the stages take them: q, qd, qdd (n, 7) and psg (n,) or None."""
+    q = _rows(q, "q"); qd = _rows(qd, "qd"); qdd = _rows(qdd, "qdd")
+    if not len(q) == len(qd) == len(qdd):
+        raise ValueError("q, qd and qdd must have the same number of rows")
+    if psg is not None:
+        psg = np.ascontiguousarray(np.asarray(psg, dtype=np.float64).reshape(-1))
+        if len(psg) != len(q):
+            raise ValueError("one psg value per row")
+    return q, qd, qdd, psg
+
+
 def pose_rows(poses):
     """(n, 4, 4) / (4, 4) homogeneous or (n, 12) rows -> contiguous (n, 12)."""
     a = np.asarray(poses, dtype=np.float64)
@@ -429,6 +441,11 @@ class Engine:
     def _check(self, rc):
         if rc != 0:
             raise TcmpError("tcmp error %d: %s" % (rc, self.L.tcmp_last_error().decode()))
+
+    def _need(self, name):
+        """An entry point an older library build (TCMP_LIB_PATH) may lack."""
+        if not hasattr(self.L, name):
+            raise TcmpError("%s: not in this library build" % name)
 
     def close(self):
         if getattr(self, "h", None):
@@ -518,8 +535,7 @@ class Engine:
         free_q7 (n_free,) shared by the poses.  Returns (q (n, max_out, 7), dist (n, max_out),
         headroom (n, max_out), ids (n, max_out; -1 past a pose's n_out), stats: one GoalStats
         per pose); self.goal_ms holds the stage's device time."""
-        if not hasattr(self.L, "tcmp_goal_search"):
-            raise TcmpError("tcmp_goal_search: not in this library build")
+        self._need("tcmp_goal_search")
         poses = pose_rows(poses)
         free_q7 = np.ascontiguousarray(np.asarray(free_q7, dtype=np.float64).reshape(-1))
         ref = np.ascontiguousarray(np.asarray(ref, dtype=np.float64).reshape(7))
@@ -638,8 +654,7 @@ class Engine:
                       max_anchors=512, passes=1):
         """tcmp_shortcut_path: force-aware shortcutting of a waypoint list (n, 7) in the scene
         set on this engine -> (waypoints, ShortcutResult)."""
-        if not hasattr(self.L, "tcmp_shortcut_path"):
-            raise TcmpError("tcmp_shortcut_path: not in this library build")
+        self._need("tcmp_shortcut_path")
         wp = _rows(waypoints, "waypoints")
         res = None if resolutions is None else np.ascontiguousarray(resolutions, dtype=np.float64)
         w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
@@ -660,8 +675,7 @@ class Engine:
     def plan_shortcut(self, max_anchors=512, passes=1):
         """tcmp_plan_shortcut: shortcut the open plan's path; the next plan_finish /
         plan_retrace uses the shortened list."""
-        if not hasattr(self.L, "tcmp_plan_shortcut"):
-            raise TcmpError("tcmp_plan_shortcut: not in this library build")
+        self._need("tcmp_plan_shortcut")
         cfg = ShortcutCfg(int(max_anchors), int(passes))
         r = ShortcutResult()
         self._check(self.L.tcmp_plan_shortcut(self.h, ctypes.byref(cfg), ctypes.byref(r)))
@@ -672,15 +686,8 @@ class Engine:
         (q, qd r, qdd x), r = sqrt(x), pass the torque test of `mode` -> (qd, qdd, psg | None,
         RetimeResult).  The rows come back scaled when the status is RETIME_OK and as given
         otherwise."""
-        if not hasattr(self.L, "tcmp_retime_traj"):
-            raise TcmpError("tcmp_retime_traj: not in this library build")
-        q = _rows(q, "q"); qd = _rows(qd, "qd"); qdd = _rows(qdd, "qdd")
-        if not len(q) == len(qd) == len(qdd):
-            raise ValueError("q, qd and qdd must have the same number of rows")
-        if psg is not None:
-            psg = np.ascontiguousarray(np.asarray(psg, dtype=np.float64).reshape(-1))
-            if len(psg) != len(q):
-                raise ValueError("one psg value per row")
+        self._need("tcmp_retime_traj")
+        q, qd, qdd, psg = _traj_arrays(q, qd, qdd, psg)
         cfg = RetimeCfg(float(min_scale), float(max_scale))
         r = RetimeResult()
         oqd = qd.copy(); oqdd = qdd.copy()
@@ -693,8 +700,7 @@ class Engine:
     def plan_retime(self, min_scale=1.0, max_scale=0.0):
         """tcmp_plan_retime: retime the rows of the open plan's last plan_finish; on RETIME_OK
         plan_fetch returns the retimed trajectory."""
-        if not hasattr(self.L, "tcmp_plan_retime"):
-            raise TcmpError("tcmp_plan_retime: not in this library build")
+        self._need("tcmp_plan_retime")
         cfg = RetimeCfg(float(min_scale), float(max_scale))
         r = RetimeResult()
         self._check(self.L.tcmp_plan_retime(self.h, ctypes.byref(cfg), ctypes.byref(r)))
@@ -712,15 +718,8 @@ class Engine:
         continuous piecewise-linear warp of psg -> (qd, qdd, psg | None, [RetimeRun],
         RetimeRunsResult).  The rows come back scaled when the status is RETIME_OK and as given
         otherwise."""
-        if not hasattr(self.L, "tcmp_retime_runs_traj"):
-            raise TcmpError("tcmp_retime_runs_traj: not in this library build")
-        q = _rows(q, "q"); qd = _rows(qd, "qd"); qdd = _rows(qdd, "qdd")
-        if not len(q) == len(qd) == len(qdd):
-            raise ValueError("q, qd and qdd must have the same number of rows")
-        if psg is not None:
-            psg = np.ascontiguousarray(np.asarray(psg, dtype=np.float64).reshape(-1))
-            if len(psg) != len(q):
-                raise ValueError("one psg value per row")
+        self._need("tcmp_retime_runs_traj")
+        q, qd, qdd, psg = _traj_arrays(q, qd, qdd, psg)
         off = np.ascontiguousarray(np.asarray(run_off, dtype=np.int64).reshape(-1))
         n_runs = max(len(off) - 1, 0)
         cfg = RetimeCfg(float(min_scale), float(max_scale))
@@ -739,8 +738,7 @@ class Engine:
         plan_finish (runs between the waypoints at rest, the gates of an OK plan_repair among
         them) -> ([RetimeRun], RetimeRunsResult); on RETIME_OK plan_fetch returns the retimed
         trajectory."""
-        if not hasattr(self.L, "tcmp_plan_retime_runs"):
-            raise TcmpError("tcmp_plan_retime_runs: not in this library build")
+        self._need("tcmp_plan_retime_runs")
         cfg = RetimeCfg(float(min_scale), float(max_scale))
         r = RetimeRunsResult()
         cap = 64
@@ -763,15 +761,8 @@ class Engine:
         dict(qd, qdd, psg | None, x, u, results=[RetimeProfileResult], ms[, coef (n, 18)]).
         A trajectory's rows come back retimed when its status is RETIME_OK and as given
         otherwise (x = 1, u = 0 there)."""
-        if not hasattr(self.L, "tcmp_retime_profile_traj"):
-            raise TcmpError("tcmp_retime_profile_traj: not in this library build")
-        q = _rows(q, "q"); qd = _rows(qd, "qd"); qdd = _rows(qdd, "qdd")
-        if not len(q) == len(qd) == len(qdd):
-            raise ValueError("q, qd and qdd must have the same number of rows")
-        if psg is not None:
-            psg = np.ascontiguousarray(np.asarray(psg, dtype=np.float64).reshape(-1))
-            if len(psg) != len(q):
-                raise ValueError("one psg value per row")
+        self._need("tcmp_retime_profile_traj")
+        q, qd, qdd, psg = _traj_arrays(q, qd, qdd, psg)
         off = np.ascontiguousarray(np.asarray([0, len(q)] if traj_off is None else traj_off,
                                               dtype=np.int64).reshape(-1))
         if len(off) < 1 or off[-1] != len(q):
@@ -797,8 +788,7 @@ class Engine:
         """tcmp_plan_retime_profile: velocity-profile retiming of the rows of the open plan's
         last plan_finish -> RetimeProfileResult; on RETIME_OK plan_fetch returns the retimed
         trajectory."""
-        if not hasattr(self.L, "tcmp_plan_retime_profile"):
-            raise TcmpError("tcmp_plan_retime_profile: not in this library build")
+        self._need("tcmp_plan_retime_profile")
         cfg = RetimeCfg(float(min_scale), float(max_scale))
         r = RetimeProfileResult()
         self._check(self.L.tcmp_plan_retime_profile(self.h, ctypes.byref(cfg), ctypes.byref(r)))
@@ -809,8 +799,7 @@ class Engine:
         segments whose rows fail collision_fn in this engine's scene put back on their chords
         (waypoint velocities zeroed) -> (q, qd, qdd, gates, RepairResult).  The arrays are None
         unless the status is REPAIR_OK (and always with check_only)."""
-        if not hasattr(self.L, "tcmp_repair_traj"):
-            raise TcmpError("tcmp_repair_traj: not in this library build")
+        self._need("tcmp_repair_traj")
         P = _rows(waypoints, "waypoints")
         cfg = RepairCfg(int(max_passes), int(bool(check_only)))
         r = RepairResult()
@@ -828,8 +817,7 @@ class Engine:
         """tcmp_plan_repair: collision repair of the rows of the open plan's last plan_finish;
         on REPAIR_OK with gates closed plan_fetch returns the repaired trajectory (and the
         engine's stored status is the new torque validation's)."""
-        if not hasattr(self.L, "tcmp_plan_repair"):
-            raise TcmpError("tcmp_plan_repair: not in this library build")
+        self._need("tcmp_plan_repair")
         cfg = RepairCfg(int(max_passes), int(bool(check_only)))
         r = RepairResult()
         self._check(self.L.tcmp_plan_repair(self.h, ctypes.byref(cfg), ctypes.byref(r)))
@@ -920,8 +908,7 @@ class Engine:
     def microbench(self):
         """Measured peaks of this device (tcmp_microbench): fp64 / packed-fp32 vector TFLOP/s
         and HBM GB/s of a 1 GiB device copy."""
-        if not hasattr(self.L, "tcmp_microbench"):
-            raise TcmpError("tcmp_microbench: not in this library build")
+        self._need("tcmp_microbench")
         out = np.zeros(4)
         self._check(self.L.tcmp_microbench(self.h, _d(out)))
         return {"fp64_tflops": float(out[0]), "fp32_tflops": float(out[1]),

@@ -193,6 +193,11 @@ __device__ __forceinline__ void load7(const double* p, double q[7]) {
   const double2 b = *reinterpret_cast<const double2*>(p + 4);
   q[0] = a.x; q[1] = a.y; q[2] = a.z; q[3] = a.w; q[4] = b.x; q[5] = b.y; q[6] = p[6];
 }
+// rows with a stride of 7 doubles (no 32-byte alignment: element loads)
+__device__ __forceinline__ void load7u(const double* p, double q[7]) {
+#pragma unroll
+  for (int k = 0; k < 7; ++k) q[k] = p[k];
+}
 __device__ __forceinline__ void store7(double* p, const double q[7]) {
 #pragma unroll
   for (int k = 0; k < 7; ++k) p[k] = q[k];
@@ -1047,9 +1052,12 @@ __device__ __forceinline__ void sincos7(const double q[7], double cq[7], double 
   for (int k = 0; k < 7; ++k) sincos(q[k], &sq[k], &cq[k]);
 }
 // a kernel template instantiated per torque mode, picked on the host
-#define TCMP_BY_MODE(K, mode) \
-  ((mode) == TCMP_TORQUE_BASE ? K<TCMP_TORQUE_BASE> : (mode) == TCMP_TORQUE_NOV ? K<TCMP_TORQUE_NOV> \
-   : (mode) == TCMP_TORQUE_DYN ? K<TCMP_TORQUE_DYN> : K<TCMP_TORQUE_RNE>)
+// (further template arguments follow the mode: TCMP_BY_MODE(k_validate, mode, 7))
+#define TCMP_BY_MODE(K, mode, ...)                                 \
+  ((mode) == TCMP_TORQUE_BASE  ? K<TCMP_TORQUE_BASE, ##__VA_ARGS__> \
+   : (mode) == TCMP_TORQUE_NOV ? K<TCMP_TORQUE_NOV, ##__VA_ARGS__>  \
+   : (mode) == TCMP_TORQUE_DYN ? K<TCMP_TORQUE_DYN, ##__VA_ARGS__>  \
+                               : K<TCMP_TORQUE_RNE, ##__VA_ARGS__>)
 
 // dynam_fn + final validation for the planner's path, one row per thread; Conf.torques follow
 // in k_traj_tau (one RNE per kernel keeps both at two waves per SIMD)
@@ -1309,15 +1317,26 @@ __global__ void k_minjerk(const double* wp, long long nwp, long long ni, double*
   }
 }
 
-template <int MODE>
+constexpr unsigned long long kNoRow = ~0ull;  // a first failing row: none
+
+// the mode's torque test on rows of STRIDE doubles: 8, the engine's padded rows, or 7, the
+// trajectory stages' packed ones
+template <int MODE, int STRIDE = 8>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE == 3 ? 1 : 2))) void k_validate(const double* q, const double* qd, const double* qdd, long long n,
                            double mass, unsigned long long* first_fail) {
+  static_assert(STRIDE == 7 || STRIDE == 8, "rows of 7 or 8 doubles");
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   double x[7], v[7], a[7], cq[7], sq[7];
-  load7(q + 8 * i, x);
-  load7(qd + 8 * i, v);
-  load7(qdd + 8 * i, a);
+  if constexpr (STRIDE == 8) {
+    load7(q + 8 * i, x);
+    load7(qd + 8 * i, v);
+    load7(qdd + 8 * i, a);
+  } else {
+    load7u(q + 7 * i, x);
+    load7u(qd + 7 * i, v);
+    load7u(qdd + 7 * i, a);
+  }
   sincos7(x, cq, sq);
   if (!torque_test_m<MODE>(mass, cq, sq, v, a)) atomicMin(first_fail, (unsigned long long)i);
 }
@@ -4367,6 +4386,7 @@ int tcmp_plan_debug_round(tcmp_handle* h, int64_t cap, double* cand, int32_t* nn
 }  // extern "C"
 
 #include "tcmp_fleet.h"
+#include "tcmp_stage.h"
 #include "tcmp_shortcut.h"
 #include "tcmp_retime.h"
 #include "tcmp_repair.h"

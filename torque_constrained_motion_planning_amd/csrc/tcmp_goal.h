@@ -348,7 +348,7 @@ int tcmp_goal_search(tcmp_handle* h, const double* poses, int32_t n_pose, const 
                         hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipMemcpyAsync(h->gs_refw.p, refw, 14 * sizeof(double), hipMemcpyHostToDevice,
                         h->stream));
-  const hipEvent_t e0 = h->mark();
+  StageSpan t(h);
   HIPCHK(hipMemsetAsync(ctl, 0, (2 + 4 * (size_t)n_pose) * sizeof(unsigned long long), h->stream));
   HIPCHK(hipMemsetAsync(oq, 0, (size_t)R * 9 * sizeof(double), h->stream));
   HIPCHK(hipMemsetAsync(h->gs_oid.p, 0xff, (size_t)R * sizeof(int), h->stream));
@@ -370,7 +370,7 @@ int tcmp_goal_search(tcmp_handle* h, const double* poses, int32_t n_pose, const 
                      h->gs_key.p, h->gs_head.p, S, (int)max_out, ctl, h->gs_lkey.p, h->gs_lid.p,
                      ctr, oq, od, oh, h->gs_oid.p);
   HIPCHK(hipGetLastError());
-  const hipEvent_t e1 = h->mark();
+  t.end();
   std::vector<unsigned long long> hc(2 + 4 * (size_t)n_pose);
   HIPCHK(hipMemcpyAsync(hc.data(), ctl, hc.size() * sizeof(unsigned long long),
                         hipMemcpyDeviceToHost, h->stream));
@@ -387,7 +387,7 @@ int tcmp_goal_search(tcmp_handle* h, const double* poses, int32_t n_pose, const 
     HIPCHK(hipMemcpyAsync(id_out, h->gs_oid.p, (size_t)R * sizeof(int), hipMemcpyDeviceToHost,
                           h->stream));
   if (int rc_s = sync_stream(h)) return rc_s;
-  const float span = rt_span(h, e0, e1);
+  const float span = t.ms();
   if (ms) *ms = span;
   if (stats) {
     for (int p = 0; p < n_pose; ++p) {

@@ -27,8 +27,6 @@ struct RpSum {
   long long stuck_seg, stuck_row;  // state 2: the lowest stuck segment and its first failing row
 };
 
-constexpr unsigned long long kRpNone = ~0ull;
-
 // every gate open, every segment dirty
 __global__ __launch_bounds__(256) void k_repair_init(long long W, int* g0, int* g1, int* dirty,
                                                      unsigned long long* first, unsigned* count) {
@@ -38,7 +36,7 @@ __global__ __launch_bounds__(256) void k_repair_init(long long W, int* g0, int* 
     g1[w] = 1;
     if (w < W - 1) {
       dirty[w] = (int)w;
-      first[w] = kRpNone;
+      first[w] = kNoRow;
       count[w] = 0u;
     }
   }
@@ -102,14 +100,14 @@ __global__ __launch_bounds__(1024) void k_repair_update(long long W, const int* 
   const int tid = threadIdx.x;
   const long long nseg = W - 1;
   if (tid == 0) {
-    s_first = kRpNone;
+    s_first = kNoRow;
     s_rows = 0;
-    s_stuck = kRpNone;
+    s_stuck = kNoRow;
     s_closed = 0;
   }
   __syncthreads();
   {
-    unsigned long long f = kRpNone, n = 0, stuck = kRpNone;
+    unsigned long long f = kNoRow, n = 0, stuck = kNoRow;
     for (long long s = tid; s < nseg; s += 1024) {
       const unsigned c = count[s];
       if (!c) continue;
@@ -123,11 +121,11 @@ __global__ __launch_bounds__(1024) void k_repair_update(long long W, const int* 
       atomicMin(&s_first, f);
       atomicAdd(&s_rows, n);
     }
-    if (stuck != kRpNone) atomicMin(&s_stuck, stuck);
+    if (stuck != kNoRow) atomicMin(&s_stuck, stuck);
   }
   __syncthreads();
   const unsigned long long rows = s_rows, stuck = s_stuck;
-  const int state = rows == 0 ? 1 : stuck != kRpNone ? 2 : 0;
+  const int state = rows == 0 ? 1 : stuck != kNoRow ? 2 : 0;
   const bool close = state == 0 && may_close;
   long long run = 0;
   if (close) {
@@ -156,7 +154,7 @@ __global__ __launch_bounds__(1024) void k_repair_update(long long W, const int* 
       }
       if (flag) {
         dirty[run + s_scan[tid] - 1] = (int)s;
-        first[s] = kRpNone;
+        first[s] = kNoRow;
         count[s] = 0u;
       }
       run += s_scan[1023];
@@ -174,32 +172,6 @@ __global__ __launch_bounds__(1024) void k_repair_update(long long W, const int* 
     r.stuck_row = state == 2 ? (long long)first[stuck] : -1;
     *out = r;
   }
-}
-
-// the mode's torque test on rows of 7 (k_validate's, for the engine's row layout)
-template <int MODE>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE == 3 ? 1 : 2)))
-void k_rp_validate(const double* __restrict__ q, const double* __restrict__ qd,
-                   const double* __restrict__ qdd, long long n, double mass,
-                   unsigned long long* first_fail) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  double x[7], v[7], a[7], cq[7], sq[7];
-#pragma unroll
-  for (int k = 0; k < 7; ++k) {
-    x[k] = q[7 * i + k];
-    v[k] = qd[7 * i + k];
-    a[k] = qdd[7 * i + k];
-  }
-  sincos7(x, cq, sq);
-  if (!torque_test_m<MODE>(mass, cq, sq, v, a)) atomicMin(first_fail, (unsigned long long)i);
-}
-
-// the plan's stored verdict on the repaired rows
-__global__ void k_rp_commit(DevState* st, const unsigned long long* first_fail) {
-  const unsigned long long ff = *first_fail;
-  st->status = ff == kRpNone ? TCMP_PLAN_OK : TCMP_PLAN_VALIDATION_FAILED;
-  st->first_fail = ff == kRpNone ? -1 : (long long)ff;
 }
 
 int rp_cfg(const tcmp_repair_cfg* cfg, int* max_passes, int* check_only) {
@@ -289,24 +261,18 @@ int rp_passes(tcmp_handle* h, const double* wp, long long W, long long ni, int m
   return 0;
 }
 
-// rp_passes between two marks (an error on the way gives the first mark back to the pool)
+// rp_passes between two marks
 int rp_run(tcmp_handle* h, const double* wp, long long W, long long ni, int max_passes,
            int check_only, tcmp_repair_result* r, int* gcur) {
   rp_clear(r);
   r->n_rows = (W - 1) * ni;
   r->n_segments = W - 1;
-  const hipEvent_t e0 = h->mark();
-  if (int rc = rp_passes(h, wp, W, ni, max_passes, check_only, r, gcur)) {
-    (void)rt_span(h, e0, nullptr);
-    return rc;
-  }
-  const hipEvent_t e1 = h->mark();
-  if (e0 && e1) {
-    if (int rc_s = sync_stream(h)) {
-      (void)rt_span(h, e0, e1);
-      return rc_s;
-    }
-    r->ms = rt_span(h, e0, e1);
+  StageSpan t(h);
+  if (int rc = rp_passes(h, wp, W, ni, max_passes, check_only, r, gcur)) return rc;
+  t.end();
+  if (t.timed()) {
+    if (int rc_s = sync_stream(h)) return rc_s;
+    r->ms = t.ms();
   }
   return 0;
 }
@@ -360,8 +326,7 @@ int tcmp_plan_repair(tcmp_handle* h, const tcmp_repair_cfg* cfg, tcmp_repair_res
   if (int rc = rp_cfg(cfg, &max_passes, &check_only)) return rc;
   rp_clear(res);
   const long long W = (long long)h->fin_W, K = (long long)h->fin_K;
-  if ((h->fin_status != TCMP_PLAN_OK && h->fin_status != TCMP_PLAN_VALIDATION_FAILED) ||
-      h->repaired || K <= 0 || W < 2) {
+  if (!stage_applicable(h) || h->repaired || W < 2) {
     res->status = TCMP_REPAIR_NOT_APPLICABLE;
     return 0;
   }
@@ -376,44 +341,25 @@ int tcmp_plan_repair(tcmp_handle* h, const tcmp_repair_cfg* cfg, tcmp_repair_res
   }
   if (int rc = h->u0.ensure(1)) return rc;
   if (int rc = h->pl_gate.ensure((size_t)W)) return rc;
-  const size_t nb = (size_t)K * 7 * sizeof(double);
-  unsigned long long ff = 0;
   // From here the engine's rows change: an error on the way leaves the plan with neither a
   // repair nor a retiming applicable until its next finish.
   h->fin_status = -1;
-  const hipEvent_t e0 = h->mark();
-  const auto replace = [&]() -> int {
-    HIPCHK(hipMemcpyAsync(h->tq.p, h->rp_o[0].p, nb, hipMemcpyDeviceToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->tqd.p, h->rp_o[1].p, nb, hipMemcpyDeviceToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->tqdd.p, h->rp_o[2].p, nb, hipMemcpyDeviceToDevice, h->stream));
-    // the plan's own copy of the gates (tcmp_plan_retime_runs derives its runs from them; a
-    // later stand-alone tcmp_repair_traj on this handle overwrites rp_gate)
-    HIPCHK(hipMemcpyAsync(h->pl_gate.p, h->rp_gate[cur].p, (size_t)W * sizeof(int),
-                          hipMemcpyDeviceToDevice, h->stream));
-    HIPCHK(hipMemsetAsync(h->u0.p, 0xff, sizeof(ff), h->stream));
-    hipLaunchKernelGGL(TCMP_BY_MODE(k_rp_validate, h->P.torque_mode), dim3(grid_for(K, 256)),
-                       dim3(256), 0, h->stream, h->tq.p, h->tqd.p, h->tqdd.p, K, h->P.mass,
-                       h->u0.p);
-    // Conf.torques of the repaired rows (the state still holds the finish's K and status)
-    hipLaunchKernelGGL(k_traj_tau, dim3(grid_for(K, 256)), dim3(256), 0, h->stream, h->st, h->tq.p,
-                       h->tqd.p, h->tqdd.p, h->ttau.p, h->kcap);
-    hipLaunchKernelGGL(k_rp_commit, dim3(1), dim3(1), 0, h->stream, h->st, h->u0.p);
-    HIPCHK(hipGetLastError());
-    return 0;
-  };
-  int rc = replace();
-  const hipEvent_t e1 = h->mark();
-  if (!rc && hipMemcpyAsync(&ff, h->u0.p, sizeof(ff), hipMemcpyDeviceToHost, h->stream) != hipSuccess)
-    rc = fail(-2, "hipMemcpyAsync of the repaired rows' first failing row");
-  rc = rc ? rc : sync_stream(h);
-  const float span = rt_span(h, e0, e1);  // (both marks go back to the pool, error or not)
-  if (rc) return rc;
-  res->ms += span;
-  res->first_fail_after = ff == kRpNone ? -1 : (int64_t)ff;
-  h->fin_status = ff == kRpNone ? TCMP_PLAN_OK : TCMP_PLAN_VALIDATION_FAILED;
+  StageSpan t(h);
+  // the plan's own copy of the gates (tcmp_plan_retime_runs derives its runs from them; a
+  // later stand-alone tcmp_repair_traj on this handle overwrites rp_gate)
+  HIPCHK(hipMemcpyAsync(h->pl_gate.p, h->rp_gate[cur].p, (size_t)W * sizeof(int),
+                        hipMemcpyDeviceToDevice, h->stream));
+  HIPCHK(hipMemsetAsync(h->u0.p, 0xff, sizeof(unsigned long long), h->stream));
+  hipLaunchKernelGGL(TCMP_BY_MODE(k_validate, h->P.torque_mode, 7), dim3(grid_for(K, 256)),
+                     dim3(256), 0, h->stream, h->rp_o[0].p, h->rp_o[1].p, h->rp_o[2].p, K,
+                     h->P.mass, h->u0.p);
+  if (int rc = plan_commit_rows(h, t, K, h->rp_o[0].p, h->rp_o[1].p, h->rp_o[2].p, nullptr,
+                                h->u0.p))
+    return rc;
+  res->ms += t.ms();
+  res->first_fail_after = h->pin->st.first_fail;
+  h->fin_status = h->pin->st.status;
   h->fin_first_fail = res->first_fail_after;
-  h->pin->st.status = h->fin_status;
-  h->pin->st.first_fail = res->first_fail_after;
   h->repaired = true;
   h->pl_gated = true;
   return 0;

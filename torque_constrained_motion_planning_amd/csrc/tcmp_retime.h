@@ -17,8 +17,6 @@
 
 namespace {
 
-constexpr double kRtEps = 1e-9;  // guard on the limit: the tolerance the RNE is pinned at
-
 // a block's, then the trajectory's, reduction
 struct RtPart {
   double x_hi, x_lo;
@@ -105,21 +103,7 @@ void k_rt_bounds(const double* __restrict__ q, const double* __restrict__ qd,
       const double gj = g[6 * i + j], tj = t[j], d = tj - gj;
       const double L = kEffort[j], Lg = L - kRtEps;
       double u, l;
-      if (d != 0.0) {
-        const double ad = fabs(d), sg = d > 0.0 ? gj : -gj;
-        u = (Lg - sg) / ad;
-        l = (-Lg - sg) / ad;
-      } else if (fabs(gj) < L) {
-        u = INFINITY;
-        l = 0.0;
-      } else {
-        u = -INFINITY;
-        l = INFINITY;
-      }
-      if (!(u == u) || !(l == l)) {  // a NaN torque: no retiming is proven
-        u = -INFINITY;
-        l = INFINITY;
-      }
+      rt_interval(gj, d, L, u, l);
       if (u < ub) {
         ub = u;
         jb = j;
@@ -223,7 +207,7 @@ void k_rt_apply(const double* __restrict__ q, const double* __restrict__ qd,
                 double* opsg, unsigned long long* first_fail) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  double c[7], v[7], a[7], cq[7], sq[7];
+  double c[7], v[7], a[7];
   {
 #pragma clang fp contract(off)
 #pragma unroll
@@ -234,16 +218,7 @@ void k_rt_apply(const double* __restrict__ q, const double* __restrict__ qd,
     }
     if (psg) opsg[i] = psg[i] * s;
   }
-  store7(oqd + 7 * i, v);
-  store7(oqdd + 7 * i, a);
-  sincos7(c, cq, sq);
-  if (!torque_test_m<MODE>(mass, cq, sq, v, a)) atomicMin(first_fail, (unsigned long long)i);
-}
-
-// the plan's stored verdict after a retiming that verified
-__global__ void k_rt_commit(DevState* st) {
-  st->status = TCMP_PLAN_OK;
-  st->first_fail = -1;
+  stage_store_test<MODE>(c, v, a, mass, i, oqd, oqdd, first_fail, (unsigned long long)i);
 }
 
 int rt_cfg(const tcmp_retime_cfg* cfg, double* min_scale, double* max_scale) {
@@ -255,19 +230,10 @@ int rt_cfg(const tcmp_retime_cfg* cfg, double* min_scale, double* max_scale) {
   return 0;
 }
 
-// the span between two marks the stream has passed; both go back to the pool (only a plan
-// finish's collect_events recycles marks, and a stand-alone call may never see one)
-float rt_span(tcmp_handle* h, hipEvent_t a, hipEvent_t b) {
-  float t = 0;
-  if (!(a && b && hipEventElapsedTime(&t, a, b) == hipSuccess)) t = 0.f;
-  for (hipEvent_t e : {a, b}) {
-    const auto it = std::find(h->ev_rec.begin(), h->ev_rec.end(), e);
-    if (e && it != h->ev_rec.end()) {
-      h->ev_rec.erase(it);
-      h->ev_pool.push_back(e);
-    }
-  }
-  return t;
+// the limits of x from the configuration (one division each, by every caller alike)
+double rt_x_max(double min_scale) { return 1.0 / (min_scale * min_scale); }
+double rt_x_cap(double max_scale) {
+  return max_scale > 0.0 ? 1.0 / (max_scale * max_scale) : 0.0;
 }
 
 // The stage on n >= 0 device rows of 7 (psg: n or null): bounds, the host's decision, then the
@@ -283,7 +249,7 @@ int rt_run(tcmp_handle* h, const double* q, const double* qd, const double* qdd,
   if (int rc = h->rt_part.ensure((size_t)(nb + 1) * sizeof(RtPart) + 8)) return rc;
   RtPart* const dpart = reinterpret_cast<RtPart*>(h->rt_part.p);
   unsigned long long* const dff = reinterpret_cast<unsigned long long*>(dpart + nb + 1);
-  const hipEvent_t e0 = h->mark();
+  StageSpan t0(h);
   if (n > 0 && mode != TCMP_TORQUE_BASE) {
     int rc = h->rt_zero.ensure((size_t)n * 7);
     rc = rc ? rc : h->rt_g.ensure((size_t)n * 6);
@@ -297,42 +263,35 @@ int rt_run(tcmp_handle* h, const double* q, const double* qd, const double* qdd,
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(&p, dpart + nb, sizeof(p), hipMemcpyDeviceToHost, h->stream));
   }
-  const hipEvent_t e1 = h->mark();
+  t0.end();
   if (int rc_s = sync_stream(h)) return rc_s;
-  r->ms = rt_span(h, e0, e1);
+  r->ms = t0.ms();
   r->x_hi = p.x_hi;
   r->x_lo = p.x_lo;
   r->n_static = p.n_static;
   r->bind_row = p.x_hi < INFINITY ? p.bind_row : -1;
   r->bind_joint = p.x_hi < INFINITY ? p.bind_joint : -1;
   r->first_fail_before = r->first_fail_after = p.first_fail == LLONG_MAX ? -1 : p.first_fail;
-  const double x_max = 1.0 / (min_scale * min_scale);
-  double x = std::min(x_max, p.x_hi);
-  if (x >= 1.0 && min_scale == 1.0) x = 1.0;
-  if (!(x > 0.0) || x < p.x_lo) {
-    r->status = TCMP_RETIME_INFEASIBLE;
-    return 0;
-  }
-  if (max_scale > 0.0 && x < 1.0 / (max_scale * max_scale)) {
-    r->status = TCMP_RETIME_OVER_CAP;
-    return 0;
-  }
-  r->x = x;
-  r->r = std::sqrt(x);
+  const RtDecision dec = rt_decide(p.x_hi, p.x_lo, rt_x_max(min_scale), rt_x_cap(max_scale),
+                                   min_scale == 1.0, max_scale > 0.0);
+  r->status = dec.status;
+  if (dec.status != TCMP_RETIME_OK) return 0;
+  r->x = dec.x;
+  r->r = std::sqrt(dec.x);
   r->s = 1.0 / r->r;
   r->first_fail_after = -1;
   if (n == 0) return 0;
   unsigned long long ff = 0;
-  const hipEvent_t e2 = h->mark();
+  StageSpan t1(h);
   HIPCHK(hipMemsetAsync(dff, 0xff, sizeof(ff), h->stream));
   hipLaunchKernelGGL(TCMP_BY_MODE(k_rt_apply, mode), dim3(nb), dim3(256), 0, h->stream, q, qd, qdd,
                      psg, n, mass, r->r, r->x, r->s, oqd, oqdd, opsg, dff);
   HIPCHK(hipGetLastError());
-  const hipEvent_t e3 = h->mark();
+  t1.end();
   HIPCHK(hipMemcpyAsync(&ff, dff, sizeof(ff), hipMemcpyDeviceToHost, h->stream));
   if (int rc_s = sync_stream(h)) return rc_s;
-  r->ms += rt_span(h, e2, e3);
-  if (ff != ~0ull) {
+  r->ms += t1.ms();
+  if (ff != kNoRow) {
     r->first_fail_after = (int64_t)ff;
     r->status = TCMP_RETIME_UNVERIFIED;
   }
@@ -362,29 +321,15 @@ int tcmp_retime_traj(tcmp_handle* h, const double* q, const double* qd, const do
   if (int rc = rt_cfg(cfg, &mn, &mx)) return rc;
   if (n > 0) {
     int rc = rt_out(h, n);
-    for (int k = 0; k < 3; ++k) rc = rc ? rc : h->rt_in[k].ensure((size_t)n * 7);
-    rc = rc ? rc : h->rt_in[3].ensure((size_t)n);
+    rc = rc ? rc : stage_upload_rows(h, q, qd, qdd, psg, n);
     if (rc) return rc;
-    const double* src[3] = {q, qd, qdd};
-    for (int k = 0; k < 3; ++k)
-      HIPCHK(hipMemcpyAsync(h->rt_in[k].p, src[k], (size_t)n * 7 * sizeof(double),
-                            hipMemcpyHostToDevice, h->stream));
-    if (psg)
-      HIPCHK(hipMemcpyAsync(h->rt_in[3].p, psg, (size_t)n * sizeof(double), hipMemcpyHostToDevice,
-                            h->stream));
   }
   if (int rc = rt_run(h, h->rt_in[0].p, h->rt_in[1].p, h->rt_in[2].p, psg ? h->rt_in[3].p : nullptr,
                       n, torque_mode, payload_mass, mn, mx, h->rt_o[0].p, h->rt_o[1].p,
                       h->rt_o[2].p, res))
     return rc;
   if (res->status != TCMP_RETIME_OK || n == 0) return 0;
-  HIPCHK(hipMemcpyAsync(qd_out, h->rt_o[0].p, (size_t)n * 7 * sizeof(double), hipMemcpyDeviceToHost,
-                        h->stream));
-  HIPCHK(hipMemcpyAsync(qdd_out, h->rt_o[1].p, (size_t)n * 7 * sizeof(double),
-                        hipMemcpyDeviceToHost, h->stream));
-  if (psg)
-    HIPCHK(hipMemcpyAsync(psg_out, h->rt_o[2].p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost,
-                          h->stream));
+  if (int rc = stage_download_rows(h, qd_out, qdd_out, psg ? psg_out : nullptr, n)) return rc;
   return sync_stream(h);
 }
 
@@ -396,7 +341,7 @@ int tcmp_plan_retime(tcmp_handle* h, const tcmp_retime_cfg* cfg, tcmp_retime_res
   if (int rc = rt_cfg(cfg, &mn, &mx)) return rc;
   memset(res, 0, sizeof(*res));
   const long long K = (long long)h->fin_K;
-  if ((h->fin_status != TCMP_PLAN_OK && h->fin_status != TCMP_PLAN_VALIDATION_FAILED) || K <= 0) {
+  if (!stage_applicable(h)) {
     res->status = TCMP_RETIME_NOT_APPLICABLE;
     res->bind_row = res->bind_joint = -1;
     res->first_fail_before = res->first_fail_after = -1;
@@ -408,23 +353,10 @@ int tcmp_plan_retime(tcmp_handle* h, const tcmp_retime_cfg* cfg, tcmp_retime_res
     return rc;
   if (res->status != TCMP_RETIME_OK) return 0;
   res->exec_time_after = res->s * h->P.exec_time;
-  const hipEvent_t e0 = h->mark();
-  HIPCHK(hipMemcpyAsync(h->tqd.p, h->rt_o[0].p, (size_t)K * 7 * sizeof(double),
-                        hipMemcpyDeviceToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->tqdd.p, h->rt_o[1].p, (size_t)K * 7 * sizeof(double),
-                        hipMemcpyDeviceToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->tpsg.p, h->rt_o[2].p, (size_t)K * sizeof(double),
-                        hipMemcpyDeviceToDevice, h->stream));
-  // Conf.torques of the scaled rows (the state still holds the finish's K and status)
-  hipLaunchKernelGGL(k_traj_tau, dim3(grid_for(K, 256)), dim3(256), 0, h->stream, h->st, h->tq.p,
-                     h->tqd.p, h->tqdd.p, h->ttau.p, h->kcap);
-  hipLaunchKernelGGL(k_rt_commit, dim3(1), dim3(1), 0, h->stream, h->st);
-  HIPCHK(hipGetLastError());
-  const hipEvent_t e1 = h->mark();
-  if (int rc_s = sync_stream(h)) return rc_s;
-  res->ms += rt_span(h, e0, e1);
-  h->pin->st.status = TCMP_PLAN_OK;
-  h->pin->st.first_fail = -1;
+  StageSpan t(h);
+  if (int rc = plan_commit_rows(h, t, K, nullptr, h->rt_o[0].p, h->rt_o[1].p, h->rt_o[2].p, nullptr))
+    return rc;
+  res->ms += t.ms();
   h->fin_status = -1;  // retimed: not again before the next finish
   return 0;
 }

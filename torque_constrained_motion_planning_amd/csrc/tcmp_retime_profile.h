@@ -8,22 +8,22 @@
 //
 // Coefficients: k_rt_bounds pass 0 (one RNE per kernel) launched three times on the same rows
 // with the rate buffers (0, 0), (0, qd), (qd, qdd): one instantiation, one instruction stream, so
-// m = d = 0 exactly on a row at rest and in nov mode.  k_rp_coef forms the differences.
-// k_rp_sweep: one wavefront per trajectory, persistent over the trajectories: the uniform floor
+// m = d = 0 exactly on a row at rest and in nov mode.  k_pf_coef forms the differences.
+// k_pf_sweep: one wavefront per trajectory, persistent over the trajectories: the uniform floor
 // (64 rows per step), the backward pass (one lane per (upper, lower) pair of lines, the fp64 DPP
 // reductions of tcmp_device.h) and the forward pass with the time sums.  The chain over the rows
 // is latency-bound: the next row's coefficients are loaded, and its lines divided out, ahead of
-// the current row's reduction.  k_rp_apply scales each row by its own (x, u) and runs the mode's
+// the current row's reduction.  k_pf_apply scales each row by its own (x, u) and runs the mode's
 // torque test.  The stand-alone call waits for the device once; the plan form twice (the
 // verdict, then the commit).
 #pragma once
 
 namespace {
 
-constexpr int kRpBadDelta = 64;  // k_rp_sweep's own status: some D_i is not > 0
+constexpr int kPfBadDelta = 64;  // k_pf_sweep's own status: some D_i is not > 0
 
 // the joint's two lines p - S x <= u <= P - S x (line: it has them, m != 0 and no NaN)
-__device__ __forceinline__ void rp_line(double g, double m, double d, double L, bool& line,
+__device__ __forceinline__ void pf_line(double g, double m, double d, double L, bool& line,
                                         double& P, double& S, double& p) {
 #pragma clang fp contract(off)
   const double Lg = L - kRtEps;
@@ -34,32 +34,11 @@ __device__ __forceinline__ void rp_line(double g, double m, double d, double L, 
   S = sd / A;
 }
 
-// the joint's direct interval in x: k_rt_bounds' ub / lb rules
-__device__ __forceinline__ void rp_direct(double g, double d, double L, double& u, double& l) {
-#pragma clang fp contract(off)
-  const double Lg = L - kRtEps;
-  if (d != 0.0) {
-    const double ad = fabs(d), sg = d > 0.0 ? g : -g;
-    u = (Lg - sg) / ad;
-    l = (-Lg - sg) / ad;
-  } else if (fabs(g) < L) {
-    u = INFINITY;
-    l = 0.0;
-  } else {
-    u = -INFINITY;
-    l = INFINITY;
-  }
-  if (!(u == u) || !(l == l)) {  // a NaN torque: nothing is proven
-    u = -INFINITY;
-    l = INFINITY;
-  }
-}
-
 // ------------------------------------------------------------------------------------------
-// k_rp_coef: one row per thread: (g, m, d) of the six joints from the three passes' torques, and
+// k_pf_coef: one row per thread: (g, m, d) of the six joints from the three passes' torques, and
 // whether the row fails the test as given (k_rt_bounds' rule on the full torque)
 // ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_rp_coef(const double* __restrict__ tg,
+__global__ __launch_bounds__(256) void k_pf_coef(const double* __restrict__ tg,
                                                  const double* __restrict__ tm,
                                                  const double* __restrict__ td, long long n,
                                                  double* coef, int* bad) {
@@ -79,7 +58,7 @@ __global__ __launch_bounds__(256) void k_rp_coef(const double* __restrict__ tg,
 }
 
 // ------------------------------------------------------------------------------------------
-// k_rp_sweep: wavefront w of the grid's G takes trajectories w, w + G, ...  Every branch around
+// k_pf_sweep: wavefront w of the grid's G takes trajectories w, w + G, ...  Every branch around
 // a wave reduction is wave-uniform (row counts, the trajectory's status), and an INFEASIBLE
 // trajectory still runs both passes to their ends.
 // Backward pass, lane = 8 k + j: k < 6 / j < 6 are the joints' upper / lower lines, 6 the link's;
@@ -87,7 +66,7 @@ __global__ __launch_bounds__(256) void k_rp_coef(const double* __restrict__ tg,
 // Forward pass: lanes 0 .. 5 the joints' upper lines, 6 .. 11 their lower lines.
 // hib / lob: the sets, written by lane 0 on the way back and read by the wave on the way forth.
 // ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_rp_sweep(
+__global__ __launch_bounds__(256) void k_pf_sweep(
     const double* __restrict__ coef, const int* __restrict__ bad, const double* __restrict__ psg,
     const long long* __restrict__ off, long long n_traj, double min_scale, double max_scale,
     double x_max, double x_cap, double* hib, double* lob, double* xo, double* uo, double* po,
@@ -108,18 +87,17 @@ __global__ __launch_bounds__(256) void k_rp_sweep(
 #pragma unroll
       for (int a = 0; a < 6; ++a) {
         double u, l;
-        rp_direct(C[18 * i + a], C[18 * i + 12 + a], kEffort[a], u, l);
+        rt_interval(C[18 * i + a], C[18 * i + 12 + a], kEffort[a], u, l);
         ub = fmin(ub, u);
         lb = fmax(lb, l);
       }
       if (bad[b + i] && ff == INFINITY) ff = (double)i;  // rows < 2^53
     }
     const double x_hi = wave_min(ub), x_lo = wave_max(lb), ffm = wave_min(ff);
-    double xu = fmin(x_max, x_hi);
-    if (xu >= 1.0 && min_scale == 1.0) xu = 1.0;
-    const int ust = (!(xu > 0.0) || xu < x_lo)           ? TCMP_RETIME_INFEASIBLE
-                    : (max_scale > 0.0 && xu < x_cap) ? TCMP_RETIME_OVER_CAP
-                                                      : TCMP_RETIME_OK;
+    const RtDecision dec =
+        rt_decide(x_hi, x_lo, x_max, x_cap, min_scale == 1.0, max_scale > 0.0);
+    const int ust = dec.status;
+    const double xu = dec.x;
     const bool anch = ust == TCMP_RETIME_OK;
     const double x_floor = anch ? xu : (max_scale > 0.0 ? x_cap : 1e-6);
     // ---- backward: the reachable sets
@@ -136,9 +114,9 @@ __global__ __launch_bounds__(256) void k_rp_sweep(
       // this row's lines (off the chain), then the row below's loads
       bool line_k, line_j;
       double Pk, Sk, pk, Pj, Sj, pj, du, dlw;
-      rp_line(gk, mk, dk, Lk, line_k, Pk, Sk, pk);
-      rp_line(gj, mj, dj, Lj, line_j, Pj, Sj, pj);
-      rp_direct(gj, dj, Lj, du, dlw);
+      pf_line(gk, mk, dk, Lk, line_k, Pk, Sk, pk);
+      pf_line(gj, mj, dj, Lj, line_j, Pj, Sj, pj);
+      rt_interval(gj, dj, Lj, du, dlw);
       if (!(gj == gj && mj == mj && dj == dj)) {
         du = -INFINITY;
         dlw = INFINITY;
@@ -202,7 +180,7 @@ __global__ __launch_bounds__(256) void k_rp_sweep(
     for (long long i = 0; i < n; ++i) {
       bool line;
       double P, S, p;
-      rp_line(gf, mf, df, Lf, line, P, S, p);
+      pf_line(gf, mf, df, Lf, line, P, S, p);
       const double dd = 2.0 * dl, hc = hn, lc = ln;
       if (i + 1 < n) {
         const double* c = C + 18 * (i + 1);
@@ -243,7 +221,7 @@ __global__ __launch_bounds__(256) void k_rp_sweep(
     if (lane == 0) {
       tcmp_retime_profile_result w;
       const bool inf = fail >= 0;
-      w.status = bad_delta ? kRpBadDelta : inf ? TCMP_RETIME_INFEASIBLE : TCMP_RETIME_OK;
+      w.status = bad_delta ? kPfBadDelta : inf ? TCMP_RETIME_INFEASIBLE : TCMP_RETIME_OK;
       w.anchored = anch ? 1 : 0;
       w.uniform_status = ust;
       w.pad = 0;
@@ -266,7 +244,7 @@ __global__ __launch_bounds__(256) void k_rp_sweep(
 }
 
 // ------------------------------------------------------------------------------------------
-// k_rp_apply: one row per thread.  The row's trajectory is the last offset at or below it
+// k_pf_apply: one row per thread.  The row's trajectory is the last offset at or below it
 // (binary search; empty trajectories share an offset with their successor); rows of a trajectory
 // that is not OK are skipped.  qd' = qd sqrt(x), qdd' = qdd x + qd u, each product rounded before
 // the add; x = 1 and u = 0 copies the row (a sum with +0 would lose the sign of a -0).  Then the
@@ -274,7 +252,7 @@ __global__ __launch_bounds__(256) void k_rp_sweep(
 // ------------------------------------------------------------------------------------------
 template <int MODE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE == 3 ? 1 : 2)))
-void k_rp_apply(const double* __restrict__ q, const double* __restrict__ qd,
+void k_pf_apply(const double* __restrict__ q, const double* __restrict__ qd,
                 const double* __restrict__ qdd, long long n, double mass,
                 const long long* __restrict__ off, long long n_traj,
                 const tcmp_retime_profile_result* __restrict__ res, const double* __restrict__ xs,
@@ -282,14 +260,9 @@ void k_rp_apply(const double* __restrict__ q, const double* __restrict__ qd,
                 unsigned long long* first_fail) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  long long lo = 0, hi = n_traj;  // off[lo] <= i < off[hi]: off[0] = 0, off[n_traj] = n
-  while (hi - lo > 1) {
-    const long long mid = (lo + hi) >> 1;
-    if (off[mid] <= i) lo = mid;
-    else hi = mid;
-  }
+  const long long lo = stage_find(off, n_traj, i);  // off[0] = 0, off[n_traj] = n
   if (res[lo].status != TCMP_RETIME_OK) return;
-  double c[7], v[7], a[7], cq[7], sq[7];
+  double c[7], v[7], a[7];
   {
 #pragma clang fp contract(off)
     const double x = xs[i], u = us[i], r = sqrt(x);
@@ -303,14 +276,11 @@ void k_rp_apply(const double* __restrict__ q, const double* __restrict__ qd,
       a[k] = keep ? a0 : ax + vu;
     }
   }
-  store7(oqd + 7 * i, v);
-  store7(oqdd + 7 * i, a);
-  sincos7(c, cq, sq);
-  if (!torque_test_m<MODE>(mass, cq, sq, v, a))
-    atomicMin(first_fail + lo, (unsigned long long)(i - off[lo]));
+  stage_store_test<MODE>(c, v, a, mass, i, oqd, oqdd, first_fail + lo,
+                         (unsigned long long)(i - off[lo]));
 }
 
-void rp_clear(tcmp_retime_profile_result* r) {
+void pf_clear(tcmp_retime_profile_result* r) {
   memset(r, 0, sizeof(*r));
   r->fail_row = r->first_fail_before = r->first_fail_after = -1;
 }
@@ -319,7 +289,7 @@ void rp_clear(tcmp_retime_profile_result* r) {
 // are in h->pf_off: the coefficients into h->pf_coef, the profile into h->pf_x / pf_u, the new
 // rows into h->rt_o[0..2], the records into h->pf_res and the new rows' first failing rows into
 // h->pf_ff.  Everything is enqueued; nothing waits.  The inputs are only read.
-int rp_enqueue(tcmp_handle* h, const double* q, const double* qd, const double* qdd,
+int pf_enqueue(tcmp_handle* h, const double* q, const double* qd, const double* qdd,
                const double* psg, long long n, long long n_traj, int mode, double mass,
                double min_scale, double max_scale) {
   int rc = rt_out(h, n);
@@ -340,7 +310,7 @@ int rp_enqueue(tcmp_handle* h, const double* q, const double* qd, const double* 
       hipLaunchKernelGGL(TCMP_BY_MODE(k_rt_bounds, mode), dim3(nb), dim3(256), 0, h->stream, q,
                          rates[k][0], rates[k][1], n, mass, 0, h->pf_t[k].p, (RtPart*)nullptr,
                          (RtRow*)nullptr);
-    hipLaunchKernelGGL(k_rp_coef, dim3(nb), dim3(256), 0, h->stream, h->pf_t[0].p, h->pf_t[1].p,
+    hipLaunchKernelGGL(k_pf_coef, dim3(nb), dim3(256), 0, h->stream, h->pf_t[0].p, h->pf_t[1].p,
                        h->pf_t[2].p, n, h->pf_coef.p, h->pf_bad.p);
   } else {
     HIPCHK(hipMemsetAsync(h->pf_coef.p, 0, (size_t)n * 18 * sizeof(double), h->stream));
@@ -348,14 +318,13 @@ int rp_enqueue(tcmp_handle* h, const double* q, const double* qd, const double* 
   }
   tcmp_retime_profile_result* const dres =
       reinterpret_cast<tcmp_retime_profile_result*>(h->pf_res.p);
-  const double x_max = 1.0 / (min_scale * min_scale);
-  const double x_cap = max_scale > 0.0 ? 1.0 / (max_scale * max_scale) : 0.0;
-  hipLaunchKernelGGL(k_rp_sweep, dim3(std::min<unsigned>(grid_for(n_traj, 4), 4096)), dim3(256), 0,
+  const double x_max = rt_x_max(min_scale), x_cap = rt_x_cap(max_scale);
+  hipLaunchKernelGGL(k_pf_sweep, dim3(std::min<unsigned>(grid_for(n_traj, 4), 4096)), dim3(256), 0,
                      h->stream, h->pf_coef.p, h->pf_bad.p, psg, h->pf_off.p, n_traj, min_scale,
                      max_scale, x_max, x_cap, h->pf_hi.p, h->pf_lo.p, h->pf_x.p, h->pf_u.p,
                      h->rt_o[2].p, dres);
   HIPCHK(hipMemsetAsync(h->pf_ff.p, 0xff, (size_t)n_traj * sizeof(unsigned long long), h->stream));
-  hipLaunchKernelGGL(TCMP_BY_MODE(k_rp_apply, mode), dim3(nb), dim3(256), 0, h->stream, q, qd, qdd,
+  hipLaunchKernelGGL(TCMP_BY_MODE(k_pf_apply, mode), dim3(nb), dim3(256), 0, h->stream, q, qd, qdd,
                      n, mass, h->pf_off.p, n_traj, dres, h->pf_x.p, h->pf_u.p, h->rt_o[0].p,
                      h->rt_o[1].p, h->pf_ff.p);
   HIPCHK(hipGetLastError());
@@ -363,11 +332,11 @@ int rp_enqueue(tcmp_handle* h, const double* q, const double* qd, const double* 
 }
 
 // the host's part of a trajectory's record once the device's and its first failing row are here
-int rp_verdict(tcmp_retime_profile_result* r, unsigned long long ff) {
-  if (r->status == kRpBadDelta) return fail(-1, "psg must ascend strictly inside a trajectory");
+int pf_verdict(tcmp_retime_profile_result* r, unsigned long long ff) {
+  if (r->status == kPfBadDelta) return fail(-1, "psg must ascend strictly inside a trajectory");
   if (r->status == TCMP_RETIME_OK) {
     r->first_fail_after = -1;
-    if (ff != ~0ull) {
+    if (ff != kNoRow) {
       r->first_fail_after = (int64_t)ff;
       r->status = TCMP_RETIME_UNVERIFIED;
     }
@@ -405,8 +374,8 @@ int tcmp_retime_profile_traj(tcmp_handle* h, const double* q, const double* qd, 
       for (int64_t i = traj_off[t]; i + 1 < traj_off[t + 1]; ++i)
         if (!(psg[i + 1] - psg[i] > 0.0))
           return fail(-1, "psg must ascend strictly inside a trajectory");
-  const double x_max = 1.0 / (mn * mn);
-  for (int64_t t = 0; t < n_traj; ++t) rp_clear(results + t);
+  const double x_max = rt_x_max(mn);
+  for (int64_t t = 0; t < n_traj; ++t) pf_clear(results + t);
   if (n == 0) {  // empty trajectories only: the uniform decision on no rows
     for (int64_t t = 0; t < n_traj; ++t) {
       results[t].anchored = 1;
@@ -414,38 +383,28 @@ int tcmp_retime_profile_traj(tcmp_handle* h, const double* q, const double* qd, 
     }
     return 0;
   }
-  int rc = h->pf_off.ensure((size_t)n_traj + 1);
-  for (int k = 0; k < 3; ++k) rc = rc ? rc : h->rt_in[k].ensure((size_t)n * 7);
-  rc = rc ? rc : h->rt_in[3].ensure((size_t)n);
-  if (rc) return rc;
-  const hipEvent_t e0 = h->mark();
-  const double* src[3] = {q, qd, qdd};
-  for (int k = 0; k < 3; ++k)
-    HIPCHK(hipMemcpyAsync(h->rt_in[k].p, src[k], (size_t)n * 7 * sizeof(double),
-                          hipMemcpyHostToDevice, h->stream));
-  if (psg)
-    HIPCHK(hipMemcpyAsync(h->rt_in[3].p, psg, (size_t)n * sizeof(double), hipMemcpyHostToDevice,
-                          h->stream));
+  if (int rc = h->pf_off.ensure((size_t)n_traj + 1)) return rc;
+  StageSpan span(h);
+  if (int rc = stage_upload_rows(h, q, qd, qdd, psg, n)) return rc;
   h->pf_hoff.assign(traj_off, traj_off + n_traj + 1);  // (alive until the wait below)
   HIPCHK(hipMemcpyAsync(h->pf_off.p, h->pf_hoff.data(), (size_t)(n_traj + 1) * sizeof(long long),
                         hipMemcpyHostToDevice, h->stream));
-  if (int rc2 = rp_enqueue(h, h->rt_in[0].p, h->rt_in[1].p, h->rt_in[2].p,
+  if (int rc2 = pf_enqueue(h, h->rt_in[0].p, h->rt_in[1].p, h->rt_in[2].p,
                            psg ? h->rt_in[3].p : nullptr, n, n_traj, torque_mode, payload_mass, mn,
                            mx))
     return rc2;
-  const hipEvent_t e1 = h->mark();
+  span.end();
   // everything comes back in one wait: the records decide on the host which rows to hand out
   const size_t o_qd = 0, o_qdd = o_qd + (size_t)n * 7, o_psg = o_qdd + (size_t)n * 7,
                o_x = o_psg + (size_t)n, o_u = o_x + (size_t)n, o_ff = o_u + (size_t)n,
                o_end = o_ff + (size_t)n_traj;
   h->pf_host.resize(o_end * sizeof(double));
   double* const hs = reinterpret_cast<double*>(h->pf_host.data());
-  const double* dsrc[5] = {h->rt_o[0].p, h->rt_o[1].p, h->rt_o[2].p, h->pf_x.p, h->pf_u.p};
-  const size_t dst[5] = {o_qd, o_qdd, o_psg, o_x, o_u}, cnt[5] = {(size_t)n * 7, (size_t)n * 7,
-                                                                   (size_t)n, (size_t)n, (size_t)n};
-  for (int k = 0; k < 5; ++k)
-    HIPCHK(hipMemcpyAsync(hs + dst[k], dsrc[k], cnt[k] * sizeof(double), hipMemcpyDeviceToHost,
-                          h->stream));
+  if (int rc = stage_download_rows(h, hs + o_qd, hs + o_qdd, hs + o_psg, n)) return rc;
+  HIPCHK(hipMemcpyAsync(hs + o_x, h->pf_x.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost,
+                        h->stream));
+  HIPCHK(hipMemcpyAsync(hs + o_u, h->pf_u.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost,
+                        h->stream));
   HIPCHK(hipMemcpyAsync(hs + o_ff, h->pf_ff.p, (size_t)n_traj * sizeof(unsigned long long),
                         hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipMemcpyAsync(results, h->pf_res.p, (size_t)n_traj * sizeof(*results),
@@ -454,15 +413,15 @@ int tcmp_retime_profile_traj(tcmp_handle* h, const double* q, const double* qd, 
     HIPCHK(hipMemcpyAsync(coef_out, h->pf_coef.p, (size_t)n * 18 * sizeof(double),
                           hipMemcpyDeviceToHost, h->stream));
   if (int rc_s = sync_stream(h)) return rc_s;
-  const double span = rt_span(h, e0, e1);
-  if (ms) *ms = span;
+  const double dt = span.ms();
+  if (ms) *ms = dt;
   const unsigned long long* const ff = reinterpret_cast<const unsigned long long*>(hs + o_ff);
   for (int64_t t = 0; t < n_traj; ++t)
-    if (results[t].status == kRpBadDelta) return rp_verdict(results + t, 0);
+    if (results[t].status == kPfBadDelta) return pf_verdict(results + t, 0);
   for (int64_t t = 0; t < n_traj; ++t) {
     tcmp_retime_profile_result& r = results[t];
-    (void)rp_verdict(&r, ff[t]);
-    r.ms = span;
+    (void)pf_verdict(&r, ff[t]);
+    r.ms = dt;
     const size_t b = (size_t)traj_off[t], m = (size_t)(traj_off[t + 1] - traj_off[t]);
     if (r.status != TCMP_RETIME_OK || m == 0) continue;
     memcpy(qd_out + 7 * b, hs + o_qd + 7 * b, m * 7 * sizeof(double));
@@ -481,51 +440,38 @@ int tcmp_plan_retime_profile(tcmp_handle* h, const tcmp_retime_cfg* cfg,
   if (!h->plan_open) return fail(-1, "no open plan");
   double mn, mx;
   if (int rc = rt_cfg(cfg, &mn, &mx)) return rc;
-  rp_clear(res);
+  pf_clear(res);
   const long long K = (long long)h->fin_K;
-  if ((h->fin_status != TCMP_PLAN_OK && h->fin_status != TCMP_PLAN_VALIDATION_FAILED) || K <= 0) {
+  if (!stage_applicable(h)) {
     res->status = TCMP_RETIME_NOT_APPLICABLE;
     return 0;
   }
   if (K > 1 && !(h->P.exec_time > 0.0))
     return fail(-1, "psg must ascend strictly inside a trajectory (execution_time is not > 0)");
   if (int rc = h->pf_off.ensure(2)) return rc;
-  const hipEvent_t e0 = h->mark();
+  StageSpan t0(h);
   h->pf_hoff.assign({0, K});  // (alive until the wait below)
   HIPCHK(hipMemcpyAsync(h->pf_off.p, h->pf_hoff.data(), 2 * sizeof(long long), hipMemcpyHostToDevice,
                         h->stream));
-  if (int rc = rp_enqueue(h, h->tq.p, h->tqd.p, h->tqdd.p, h->tpsg.p, K, 1, h->P.torque_mode,
+  if (int rc = pf_enqueue(h, h->tq.p, h->tqd.p, h->tqdd.p, h->tpsg.p, K, 1, h->P.torque_mode,
                           h->P.mass, mn, mx))
     return rc;
-  const hipEvent_t e1 = h->mark();
+  t0.end();
   unsigned long long ff = 0;
   HIPCHK(hipMemcpyAsync(res, h->pf_res.p, sizeof(*res), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipMemcpyAsync(&ff, h->pf_ff.p, sizeof(ff), hipMemcpyDeviceToHost, h->stream));
   if (int rc_s = sync_stream(h)) return rc_s;
-  const double span = rt_span(h, e0, e1);
-  if (int rc = rp_verdict(res, ff)) return rc;
-  res->ms = span;
+  if (int rc = pf_verdict(res, ff)) return rc;
+  res->ms = t0.ms();
   if (res->status != TCMP_RETIME_OK) return 0;
   res->exec_time_after = res->time_before != 0.0
                              ? h->P.exec_time * res->time_after / res->time_before
                              : h->P.exec_time;
-  const hipEvent_t e2 = h->mark();
-  HIPCHK(hipMemcpyAsync(h->tqd.p, h->rt_o[0].p, (size_t)K * 7 * sizeof(double),
-                        hipMemcpyDeviceToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->tqdd.p, h->rt_o[1].p, (size_t)K * 7 * sizeof(double),
-                        hipMemcpyDeviceToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->tpsg.p, h->rt_o[2].p, (size_t)K * sizeof(double),
-                        hipMemcpyDeviceToDevice, h->stream));
-  // Conf.torques of the new rows (the state still holds the finish's K and status)
-  hipLaunchKernelGGL(k_traj_tau, dim3(grid_for(K, 256)), dim3(256), 0, h->stream, h->st, h->tq.p,
-                     h->tqd.p, h->tqdd.p, h->ttau.p, h->kcap);
-  hipLaunchKernelGGL(k_rt_commit, dim3(1), dim3(1), 0, h->stream, h->st);
-  HIPCHK(hipGetLastError());
-  const hipEvent_t e3 = h->mark();
-  if (int rc_s = sync_stream(h)) return rc_s;
-  res->ms += rt_span(h, e2, e3);
-  h->pin->st.status = TCMP_PLAN_OK;
-  h->pin->st.first_fail = -1;
+  StageSpan t1(h);
+  if (int rc = plan_commit_rows(h, t1, K, nullptr, h->rt_o[0].p, h->rt_o[1].p, h->rt_o[2].p,
+                                nullptr))
+    return rc;
+  res->ms += t1.ms();
   h->fin_status = -1;  // retimed: not again before the next finish
   return 0;
 }

@@ -143,15 +143,8 @@ void k_rt_runs_apply(const double* __restrict__ q, const double* __restrict__ qd
                      unsigned long long* first_fail) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  const long long* const off = dro + 1;
-  long long lo = 0, hi = dro[0];  // off[lo] <= i < off[hi]: off[0] = 0, off[n_runs] = n
-  while (hi - lo > 1) {
-    const long long mid = (lo + hi) >> 1;
-    if (off[mid] <= i) lo = mid;
-    else hi = mid;
-  }
-  const RtRunTab t = tab[lo];
-  double c[7], v[7], a[7], cq[7], sq[7];
+  const RtRunTab t = tab[stage_find(dro + 1, dro[0], i)];  // off[0] = 0, off[n_runs] = n
+  double c[7], v[7], a[7];
   {
 #pragma clang fp contract(off)
 #pragma unroll
@@ -165,10 +158,7 @@ void k_rt_runs_apply(const double* __restrict__ q, const double* __restrict__ qd
       opsg[i] = (t.s == 1.0 && t.O == t.o) ? p : t.O + (p - t.o) * t.s;
     }
   }
-  store7(oqd + 7 * i, v);
-  store7(oqdd + 7 * i, a);
-  sincos7(c, cq, sq);
-  if (!torque_test_m<MODE>(mass, cq, sq, v, a)) atomicMin(first_fail, (unsigned long long)i);
+  stage_store_test<MODE>(c, v, a, mass, i, oqd, oqdd, first_fail, (unsigned long long)i);
 }
 
 void rr_clear(tcmp_retime_runs_result* r) {
@@ -186,7 +176,7 @@ int rr_run(tcmp_handle* h, const double* q, const double* qd, const double* qdd,
            const double* psg, long long n, long long max_runs, int mode, double mass,
            double min_scale, double max_scale, double* oqd, double* oqdd, double* opsg,
            tcmp_retime_run* runs, long long cap_runs, tcmp_retime_runs_result* r) {
-  const double x_max = 1.0 / (min_scale * min_scale);
+  const double x_max = rt_x_max(min_scale), x_cap = rt_x_cap(max_scale);
   r->n_rows = n;
   if (max_runs == 0) {  // no rows
     r->x_min = x_max;
@@ -214,7 +204,7 @@ int rr_run(tcmp_handle* h, const double* q, const double* qd, const double* qdd,
   RtPart* const hpart = reinterpret_cast<RtPart*>(h->rr_host.data() + o_part);
   double* const horg = reinterpret_cast<double*>(h->rr_host.data() + o_org);
   RtRunTab* const htab = reinterpret_cast<RtRunTab*>(h->rr_host.data() + o_tab);
-  const hipEvent_t e0 = h->mark();
+  StageSpan t0(h);
   if (mode != TCMP_TORQUE_BASE) {
     rc = h->rt_zero.ensure((size_t)n * 7);
     rc = rc ? rc : h->rt_g.ensure((size_t)n * 6);
@@ -236,14 +226,14 @@ int rr_run(tcmp_handle* h, const double* q, const double* qd, const double* qdd,
                         h->stream));
   HIPCHK(hipMemcpyAsync(horg, h->rr_org.p, (size_t)max_runs * sizeof(double),
                         hipMemcpyDeviceToHost, h->stream));
-  const hipEvent_t e1 = h->mark();
+  t0.end();
   if (int rc_s = sync_stream(h)) return rc_s;
-  r->ms = rt_span(h, e0, e1);
+  r->ms = t0.ms();
   const long long nr = hoff[0];
   if (nr < 1 || nr > max_runs) return fail(-5, "run offsets out of range");
   r->n_runs = nr;
   if (runs && cap_runs < nr) return fail(-4, "cap_runs below the number of runs");
-  // every run's decision (tcmp_retime.h rt_run's, per run)
+  // every run's decision (rt_decide, as rt_run's for the trajectory)
   long long ffb = LLONG_MAX, bad_inf = -1, bad_cap = -1;
   for (long long k = 0; k < nr; ++k) {
     const RtPart& p = hpart[k];
@@ -258,17 +248,16 @@ int rr_run(tcmp_handle* h, const double* q, const double* qd, const double* qdd,
     u.bind_joint = p.x_hi < INFINITY ? p.bind_joint : -1;
     u.first_fail = p.first_fail == LLONG_MAX ? -1 : p.first_fail;
     if (u.first_fail >= 0) ffb = std::min<long long>(ffb, u.first_fail);
-    double x = std::min(x_max, p.x_hi);
-    if (x >= 1.0 && min_scale == 1.0) x = 1.0;
-    if (!(x > 0.0) || x < p.x_lo) {
-      u.status = TCMP_RETIME_INFEASIBLE;
+    const RtDecision dec =
+        rt_decide(p.x_hi, p.x_lo, x_max, x_cap, min_scale == 1.0, max_scale > 0.0);
+    u.status = dec.status;
+    if (dec.status == TCMP_RETIME_INFEASIBLE) {
       if (bad_inf < 0) bad_inf = k;
-    } else if (max_scale > 0.0 && x < 1.0 / (max_scale * max_scale)) {
-      u.status = TCMP_RETIME_OVER_CAP;
+    } else if (dec.status == TCMP_RETIME_OVER_CAP) {
       if (bad_cap < 0) bad_cap = k;
     } else {
-      u.x = x;
-      u.r = std::sqrt(x);
+      u.x = dec.x;
+      u.r = std::sqrt(dec.x);
       u.s = 1.0 / u.r;
     }
     htab[k] = RtRunTab{u.r, u.x, u.s, 0.0, 0.0};
@@ -298,18 +287,18 @@ int rr_run(tcmp_handle* h, const double* q, const double* qd, const double* qdd,
   }
   r->first_fail_after = -1;
   unsigned long long ff = 0;
-  const hipEvent_t e2 = h->mark();
+  StageSpan t1(h);
   HIPCHK(hipMemcpyAsync(dtab, htab, (size_t)nr * sizeof(RtRunTab), hipMemcpyHostToDevice,
                         h->stream));
   HIPCHK(hipMemsetAsync(dff, 0xff, sizeof(ff), h->stream));
   hipLaunchKernelGGL(TCMP_BY_MODE(k_rt_runs_apply, mode), dim3(nb), dim3(256), 0, h->stream, q, qd,
                      qdd, psg, n, mass, h->rr_off.p, dtab, oqd, oqdd, opsg, dff);
   HIPCHK(hipGetLastError());
-  const hipEvent_t e3 = h->mark();
+  t1.end();
   HIPCHK(hipMemcpyAsync(&ff, dff, sizeof(ff), hipMemcpyDeviceToHost, h->stream));
   if (int rc_s = sync_stream(h)) return rc_s;
-  r->ms += rt_span(h, e2, e3);
-  if (ff != ~0ull) {
+  r->ms += t1.ms();
+  if (ff != kNoRow) {
     r->first_fail_after = (int64_t)ff;
     r->status = TCMP_RETIME_UNVERIFIED;
   }
@@ -359,17 +348,9 @@ int tcmp_retime_runs_traj(tcmp_handle* h, const double* q, const double* qd, con
   const long long nr = n_runs;  // (read by the upload below: alive until rr_run's first wait)
   if (n > 0) {
     int rc = rt_out(h, n);
-    for (int k = 0; k < 3; ++k) rc = rc ? rc : h->rt_in[k].ensure((size_t)n * 7);
-    rc = rc ? rc : h->rt_in[3].ensure((size_t)n);
     rc = rc ? rc : h->rr_off.ensure((size_t)n_runs + 2);
+    rc = rc ? rc : stage_upload_rows(h, q, qd, qdd, psg, n);
     if (rc) return rc;
-    const double* src[3] = {q, qd, qdd};
-    for (int k = 0; k < 3; ++k)
-      HIPCHK(hipMemcpyAsync(h->rt_in[k].p, src[k], (size_t)n * 7 * sizeof(double),
-                            hipMemcpyHostToDevice, h->stream));
-    if (psg)
-      HIPCHK(hipMemcpyAsync(h->rt_in[3].p, psg, (size_t)n * sizeof(double), hipMemcpyHostToDevice,
-                            h->stream));
     HIPCHK(hipMemcpyAsync(h->rr_off.p, &nr, sizeof(nr), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(h->rr_off.p + 1, run_off, (size_t)(n_runs + 1) * sizeof(long long),
                           hipMemcpyHostToDevice, h->stream));
@@ -379,13 +360,7 @@ int tcmp_retime_runs_traj(tcmp_handle* h, const double* q, const double* qd, con
                       h->rt_o[2].p, runs, n_runs, res))
     return rc;
   if (res->status != TCMP_RETIME_OK || n == 0) return 0;
-  HIPCHK(hipMemcpyAsync(qd_out, h->rt_o[0].p, (size_t)n * 7 * sizeof(double), hipMemcpyDeviceToHost,
-                        h->stream));
-  HIPCHK(hipMemcpyAsync(qdd_out, h->rt_o[1].p, (size_t)n * 7 * sizeof(double),
-                        hipMemcpyDeviceToHost, h->stream));
-  if (psg)
-    HIPCHK(hipMemcpyAsync(psg_out, h->rt_o[2].p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost,
-                          h->stream));
+  if (int rc = stage_download_rows(h, qd_out, qdd_out, psg ? psg_out : nullptr, n)) return rc;
   return sync_stream(h);
 }
 
@@ -398,8 +373,7 @@ int tcmp_plan_retime_runs(tcmp_handle* h, const tcmp_retime_cfg* cfg, tcmp_retim
   if (int rc = rt_cfg(cfg, &mn, &mx)) return rc;
   rr_clear(res);
   const long long W = (long long)h->fin_W, K = (long long)h->fin_K;
-  if ((h->fin_status != TCMP_PLAN_OK && h->fin_status != TCMP_PLAN_VALIDATION_FAILED) || K <= 0 ||
-      W < 2 || K % (W - 1) != 0) {
+  if (!stage_applicable(h) || W < 2 || K % (W - 1) != 0) {
     res->status = TCMP_RETIME_NOT_APPLICABLE;
     return 0;
   }
@@ -415,23 +389,11 @@ int tcmp_plan_retime_runs(tcmp_handle* h, const tcmp_retime_cfg* cfg, tcmp_retim
     return rc2;
   if (res->status != TCMP_RETIME_OK) return 0;
   res->exec_time_after = h->P.exec_time * res->time_ratio;
-  const hipEvent_t e0 = h->mark();
-  HIPCHK(hipMemcpyAsync(h->tqd.p, h->rt_o[0].p, (size_t)K * 7 * sizeof(double),
-                        hipMemcpyDeviceToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->tqdd.p, h->rt_o[1].p, (size_t)K * 7 * sizeof(double),
-                        hipMemcpyDeviceToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->tpsg.p, h->rt_o[2].p, (size_t)K * sizeof(double),
-                        hipMemcpyDeviceToDevice, h->stream));
-  // Conf.torques of the scaled rows (the state still holds the finish's K and status)
-  hipLaunchKernelGGL(k_traj_tau, dim3(grid_for(K, 256)), dim3(256), 0, h->stream, h->st, h->tq.p,
-                     h->tqd.p, h->tqdd.p, h->ttau.p, h->kcap);
-  hipLaunchKernelGGL(k_rt_commit, dim3(1), dim3(1), 0, h->stream, h->st);
-  HIPCHK(hipGetLastError());
-  const hipEvent_t e1 = h->mark();
-  if (int rc_s = sync_stream(h)) return rc_s;
-  res->ms += rt_span(h, e0, e1);
-  h->pin->st.status = TCMP_PLAN_OK;
-  h->pin->st.first_fail = -1;
+  StageSpan t(h);
+  if (int rc3 = plan_commit_rows(h, t, K, nullptr, h->rt_o[0].p, h->rt_o[1].p, h->rt_o[2].p,
+                                 nullptr))
+    return rc3;
+  res->ms += t.ms();
   h->fin_status = -1;  // retimed: not again before the next finish
   return 0;
 }

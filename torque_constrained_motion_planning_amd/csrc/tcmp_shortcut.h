@@ -63,12 +63,6 @@ __device__ __forceinline__ long long sc_anchor(const ScGrid& g, int k) {
   return v < g.n - 1 ? v : g.n - 1;
 }
 
-// waypoint rows have a stride of 7 doubles (no 32-byte alignment: element loads)
-__device__ __forceinline__ void load7u(const double* p, double q[7]) {
-#pragma unroll
-  for (int k = 0; k < 7; ++k) q[k] = p[k];
-}
-
 // ------------------------------------------------------------------------------------------
 // k_sc_chords: chord e -> its anchor pair, its from / to rows as EdgeJob reads them, its
 // length; thread e < A - 1 also sums original hop e
@@ -301,7 +295,7 @@ int sc_run(tcmp_handle* h, const PlanParams& P, DevState* st, double* const bufs
   if (int rc = h->sc_stats.ensure(sizeof(ScStats))) return rc;
   ScStats* dstats = reinterpret_cast<ScStats*>(h->sc_stats.p);
   HIPCHK(hipMemcpyAsync(h->dPx, &P, sizeof(P), hipMemcpyHostToDevice, h->stream));
-  const hipEvent_t ev0 = h->mark();
+  StageSpan t(h);
   r->n_before = r->n_after = n;
   for (int p = 0; p < passes; ++p) {
     const ScGrid g = sc_grid(n, a_max);
@@ -359,11 +353,10 @@ int sc_run(tcmp_handle* h, const PlanParams& P, DevState* st, double* const bufs
     r->chord_steps += steps;
     if (s.used == 0) break;
   }
-  const hipEvent_t ev1 = h->mark();
-  if (ev0 && ev1) {
+  t.end();
+  if (t.timed()) {
     if (int rc_s = sync_stream(h)) return rc_s;
-    float t = 0;
-    if (hipEventElapsedTime(&t, ev0, ev1) == hipSuccess) r->ms = t;
+    r->ms = t.ms();
   }
   return 0;
 }
