@@ -29,6 +29,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -1344,10 +1345,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE == 3 ?
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
+// The owners below free what they hold when they are destroyed: a member of the handle needs no
+// line in tcmp_destroy.  None can be copied.
 template <typename T>
 struct DBuf {
   T* p = nullptr;
   size_t n = 0;
+  DBuf() = default;
+  DBuf(const DBuf&) = delete;
+  DBuf& operator=(const DBuf&) = delete;
+  ~DBuf() { release(); }  // (not ensure()'s capture check: nothing is destroyed under a capture)
   int ensure(size_t want) {
     if (want <= n) return 0;
     // a captured graph must not bake in a buffer freed under it, and hipFree / hipMalloc
@@ -1366,6 +1373,72 @@ struct DBuf {
     p = nullptr;
     n = 0;
   }
+};
+
+// pinned host memory of n bytes, grown like a DBuf
+struct PinBuf {
+  void* p = nullptr;
+  size_t n = 0;
+  PinBuf() = default;
+  PinBuf(const PinBuf&) = delete;
+  PinBuf& operator=(const PinBuf&) = delete;
+  ~PinBuf() {
+    if (p) (void)hipHostFree(p);
+  }
+  int ensure(size_t bytes) {
+    if (bytes <= n) return 0;
+    if (p) HIPCHK(hipHostFree(p));
+    p = nullptr;
+    n = 0;
+    HIPCHK(hipHostMalloc(&p, bytes));
+    n = bytes;
+    return 0;
+  }
+};
+
+// one T in device memory, allocated on the first ensure(); reads as the T* it holds
+template <typename T>
+struct DevObj {
+  T* p = nullptr;
+  DevObj() = default;
+  DevObj(const DevObj&) = delete;
+  DevObj& operator=(const DevObj&) = delete;
+  ~DevObj() {
+    if (p) (void)hipFree(p);
+  }
+  int ensure() {
+    if (!p) HIPCHK(hipMalloc(&p, sizeof(T)));
+    return 0;
+  }
+  operator T*() const { return p; }
+  T* operator->() const { return p; }
+};
+
+// an event, created on the first ensure()
+struct Event {
+  hipEvent_t e = nullptr;
+  Event() = default;
+  Event(const Event&) = delete;
+  Event& operator=(const Event&) = delete;
+  ~Event() {
+    if (e) (void)hipEventDestroy(e);
+  }
+  int ensure(unsigned flags) {
+    if (!e) HIPCHK(hipEventCreateWithFlags(&e, flags));
+    return 0;
+  }
+};
+
+// the handle's stream (tcmp_create makes it); reads as the hipStream_t it holds
+struct Stream {
+  hipStream_t s = nullptr;
+  Stream() = default;
+  Stream(const Stream&) = delete;
+  Stream& operator=(const Stream&) = delete;
+  ~Stream() {
+    if (s) (void)hipStreamDestroy(s);
+  }
+  operator hipStream_t() const { return s; }
 };
 
 // F_NNSCAN times the k_nearest_wave launch alone (inside F_NEAREST, not added to totals)
@@ -1399,7 +1472,9 @@ struct RoundGraph {
 
 struct tcmp_handle {
   int device = 0;
-  hipStream_t stream = nullptr;
+  // Members are destroyed in reverse declaration order: the stream is declared before every
+  // buffer, pinned block and event, so it outlives them all.  Keep it second.
+  Stream stream;
   int cu_count = 0;
   DBuf<double> verts, planes, edges;
   DBuf<double> obs;
@@ -1438,12 +1513,11 @@ struct tcmp_handle {
   bool use_sph = true;  // TCMP_SPHERES=0 turns the certificate off (A/B)
   std::vector<double> sph_h;
   DBuf<float> sph;
-  DevState* st = nullptr;
+  DevObj<DevState> st;
   // plan: parameters on the host and their device copies (kernels read dP, so a captured
   // round graph replays for any query of the same shape); dPx for the standalone entry points
   PlanParams P{};
-  PlanParams* dP = nullptr;
-  PlanParams* dPx = nullptr;
+  DevObj<PlanParams> dP, dPx;
   bool plan_open = false;
   int max_batch = 0;
   DBuf<double> cfg, tgt;
@@ -1465,9 +1539,9 @@ struct tcmp_handle {
   DBuf<int> cflag, cid, cstart, sflag, sid, sstart;
   DBuf<unsigned long long> ckey;
   DBuf<unsigned char> sort_tmp;
-  DevState* st_nn = nullptr;  // state of tcmp_nearest's standalone index (keeps a plan's intact)
+  DevObj<DevState> st_nn;  // state of tcmp_nearest's standalone index (keeps a plan's intact)
   int nn_waves_per_cu = (kNnBlock / 64) * TCMP_NN_MINB;  // the scan's resident waves per CU
-  hipEvent_t ins_ev = nullptr;     // open F_INSERT mark between round_search and round_finish
+  hipEvent_t ins_ev = nullptr;     // open F_INSERT mark between round_search and round_finish (a pool event)
   DBuf<long long> xch;             // shared-tree round exchange slots (k_sr_*)
   DBuf<int> cs_hist, cs_hoff;      // counting-sort histogram (kept zeroed) and bin offsets
   // pinned host staging of a plan's begin / finish (async copies, one host wait per call)
@@ -1480,7 +1554,8 @@ struct tcmp_handle {
     DevState st;
     PlanParams P;
   };
-  Pin* pin = nullptr;
+  PinBuf pin_mem;
+  Pin* pin() const { return static_cast<Pin*>(pin_mem.p); }
   DBuf<unsigned char> dpin;     // the Pin block's device copy (plan_begin: one upload)
   size_t fin_W = 0, fin_K = 0;  // the finished plan's waypoint / trajectory rows (plan_fetch)
   long long kcap = 0;           // trajectory rows allocated at plan_begin (exec_time * 1000 + 2)
@@ -1517,17 +1592,15 @@ struct tcmp_handle {
   DBuf<unsigned char> f_desc;
   DBuf<long long> f_off;
   std::vector<unsigned char> f_host;
-  hipEvent_t dep_ev = nullptr;
+  Event dep_ev;
   int fused_plans = 0;  // plans of the fused rounds the open plan grew in (0: none)
   // pinned host staging of the scene's records (upload_scene: no host wait; the buffer is
   // reused once the event of its last copy has passed)
-  void* scene_pin = nullptr;
-  size_t scene_pin_n = 0;
-  hipEvent_t scene_ev = nullptr;
+  PinBuf scene_pin;
+  Event scene_ev;
   // pinned staging of a finished plan's trajectory rows (tcmp_plan_fetch: DMA copies instead of
   // blit kernels through pageable memory), sized at plan_begin for kcap rows
-  void* fetch_pin = nullptr;
-  size_t fetch_pin_n = 0;
+  PinBuf fetch_pin;
   // force-aware shortcutting (tcmp_shortcut.h): the second waypoint buffers, the chords' edge
   // job, the pass's tables, the scratch state the chords' launch counts into; sc_live: the open
   // plan's waypoint buffer holds a shortened list (tcmp_plan_shortcut) the finish must keep
@@ -1535,7 +1608,7 @@ struct tcmp_handle {
   DBuf<int> sc_nsafe, sc_nsteps;
   DBuf<int2> sc_kl, sc_hops;
   DBuf<unsigned char> sc_stats;
-  DevState* st_sc = nullptr;
+  DevObj<DevState> st_sc;
   bool sc_live = false;
   // torque-feasible retiming (tcmp_retime.h): the stand-alone call's rows, the scaled rows, the
   // zero rates and static torques of the bounds passes, the blocks' partials; fin_status: the
@@ -1555,7 +1628,7 @@ struct tcmp_handle {
   DBuf<unsigned long long> rp_first;
   DBuf<unsigned> rp_count;
   DBuf<unsigned char> rp_sum;
-  void* rp_pin = nullptr;
+  PinBuf rp_pin;
   long long fin_first_fail = -1;
   bool repaired = false;
   // per-run retiming (tcmp_retime_runs.h): the plan's own copy of the gates its last OK repair
@@ -1683,6 +1756,20 @@ struct tcmp_handle {
     for (auto e : rg.owned) (void)hipEventDestroy(e);
     rg = RoundGraph{};
   }
+
+  tcmp_handle() = default;
+  tcmp_handle(const tcmp_handle&) = delete;
+  tcmp_handle& operator=(const tcmp_handle&) = delete;
+  // What no member owns by itself: the round graph and the pooled events (ins_ev is one of
+  // them).  Then the members go, in reverse declaration order and the stream after all the
+  // buffers.  tcmp_destroy drains the stream first; tcmp_create's failure exits leave nothing
+  // queued that outlives their own waits.
+  ~tcmp_handle() {
+    (void)hipSetDevice(device);
+    drop_graph();
+    for (auto e : ev_rec) (void)hipEventDestroy(e);
+    for (auto e : ev_pool) (void)hipEventDestroy(e);
+  }
 };
 
 namespace {
@@ -1715,7 +1802,27 @@ int upload7(tcmp_handle* h, DBuf<double>& buf, const double* src, long long n) {
     for (int k = 0; k < 7; ++k) tmp[8 * i + k] = src[7 * i + k];
   HIPCHK(hipMemcpyAsync(buf.p, tmp.data(), tmp.size() * sizeof(double), hipMemcpyHostToDevice,
                         h->stream));
-  if (int rc_s = sync_stream(h)) return rc_s;
+  return sync_stream(h);
+}
+
+// count elements of T, host -> device: buf grown to hold them, then an asynchronous copy on the
+// handle's stream.  No wait: src must stay as it is until the caller's next one.  A caller with
+// several puts its plain ensure()s first, so the only failure after a queued copy is a later
+// upload's growth, and that one waits before it returns: the caller then gives up its arrays.
+template <typename T>
+int upload(tcmp_handle* h, DBuf<T>& buf, const void* src, size_t count) {
+  if (int rc = buf.ensure(count)) {
+    if (!t_capturing) (void)hipStreamSynchronize(h->stream);
+    return rc;
+  }
+  HIPCHK(hipMemcpyAsync(buf.p, src, count * sizeof(T), hipMemcpyHostToDevice, h->stream));
+  return 0;
+}
+
+// count elements of T, device -> host, likewise: dst holds them after the caller's next wait
+template <typename T>
+int download(tcmp_handle* h, T* dst, const void* src, size_t count) {
+  HIPCHK(hipMemcpyAsync(dst, src, count * sizeof(T), hipMemcpyDeviceToHost, h->stream));
   return 0;
 }
 
@@ -1976,10 +2083,11 @@ __global__ __launch_bounds__(256) void k_edge_order_keys(const PlanParams* __res
 
 // reset_counter = false: the plan's k_nn_home already cleared the work counter
 // kernel_begin (nullable): an event recorded between k_edge_records and k_edges (timing on)
-int launch_edges(tcmp_handle* h, const EdgeJob& J, const PlanParams* dP, bool reset_counter = true,
-                 hipEvent_t* kernel_begin = nullptr) {
+// st: the state the launch counts into (the plan's, or the shortcut pass's scratch state)
+int launch_edges(tcmp_handle* h, DevState* st, const EdgeJob& J, const PlanParams* dP,
+                 bool reset_counter = true, hipEvent_t* kernel_begin = nullptr) {
   if (J.n <= 0) return 0;
-  if (reset_counter) HIPCHK(hipMemsetAsync(&h->st->work_counter, 0, sizeof(int), h->stream));
+  if (reset_counter) HIPCHK(hipMemsetAsync(&st->work_counter, 0, sizeof(int), h->stream));
   // persistent grid bounded by residency (256-thread blocks hold one wave per SIMD each).
   // Above it, lanes refill from the longest-first queue; below it, one edge per lane --
   // halving the lanes of a small round (65,536 edges) would leave half the chip idle.
@@ -2003,7 +2111,7 @@ int launch_edges(tcmp_handle* h, const EdgeJob& J, const PlanParams* dP, bool re
               : split == 2 ? (mk ? k_edges<true, 2> : k_edges<false, 2>)
                            : (mk ? k_edges<true, 1> : k_edges<false, 1>);
   hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), lds_bytes(h), h->stream, J, dP,
-                     h->scene(), h->geo(), h->st);
+                     h->scene(), h->geo(), st);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -2072,8 +2180,7 @@ int tcmp_debug_counters(tcmp_handle* h, uint64_t* out, int32_t n) {
 
 int tcmp_synchronize(tcmp_handle* h) {
   TCMP_ENTER(h);
-  if (int rc_s = sync_stream(h)) return rc_s;
-  return 0;
+  return sync_stream(h);
 }
 
 int tcmp_device_count(int* n) {
@@ -2090,16 +2197,18 @@ int tcmp_create(int device, tcmp_handle** out) {
   HIPCHK(hipGetDeviceCount(&nd));
   if (device < 0 || device >= nd) return fail(-1, "device index out of range");
   HIPCHK(hipSetDevice(device));
-  tcmp_handle* h = new tcmp_handle();
+  // the handle's destructor frees whatever a failing step below leaves allocated
+  std::unique_ptr<tcmp_handle> owner(new tcmp_handle());
+  tcmp_handle* const h = owner.get();
   h->device = device;
   hipDeviceProp_t prop;
   HIPCHK(hipGetDeviceProperties(&prop, device));
   h->cu_count = prop.multiProcessorCount;
-  HIPCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+  HIPCHK(hipStreamCreateWithFlags(&h->stream.s, hipStreamNonBlocking));
   int rc = h->verts.ensure(TCMP_TOTAL_VERTS * 4);
   rc = rc ? rc : h->planes.ensure(TCMP_TOTAL_PLANES * 8);
   rc = rc ? rc : h->edges.ensure(TCMP_TOTAL_EDGES * 16);
-  if (rc) { delete h; return rc; }
+  if (rc) return rc;
   HIPCHK(hipMemcpy(h->verts.p, tcmp_geo_verts, sizeof(tcmp_geo_verts), hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(h->planes.p, tcmp_geo_planes, sizeof(tcmp_geo_planes), hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(h->edges.p, tcmp_geo_edges, sizeof(tcmp_geo_edges), hipMemcpyHostToDevice));
@@ -2113,7 +2222,7 @@ int tcmp_create(int device, tcmp_handle** out) {
     rc = h->verts32.ensure(v32.size());
     rc = rc ? rc : h->planes32.ensure(p32.size());
     rc = rc ? rc : h->eidx.ensure(4 * TCMP_TOTAL_EDGES);
-    if (rc) { delete h; return rc; }
+    if (rc) return rc;
     HIPCHK(hipMemcpy(h->verts32.p, v32.data(), v32.size() * 4, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(h->planes32.p, p32.data(), p32.size() * 4, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(h->eidx.p, tcmp_geo_edge_idx, sizeof(tcmp_geo_edge_idx), hipMemcpyHostToDevice));
@@ -2125,7 +2234,7 @@ int tcmp_create(int device, tcmp_handle** out) {
           ev[4 * e + k] = (float)(tcmp_geo_verts[4 * q[1] + k] - tcmp_geo_verts[4 * q[0] + k]);
       }
       rc = h->geo_ev.ensure(ev.size());
-      if (rc) { delete h; return rc; }
+      if (rc) return rc;
       HIPCHK(hipMemcpy(h->geo_ev.p, ev.data(), ev.size() * 4, hipMemcpyHostToDevice));
     }
     // link LOD hulls (fp32 vertices [V][3], planes float4, edge rows)
@@ -2139,7 +2248,7 @@ int tcmp_create(int device, tcmp_handle** out) {
       rc = h->lodv3[i].ensure(a.size());
       rc = rc ? rc : h->lodpl[i].ensure(b.size());
       rc = rc ? rc : h->lodei[i].ensure(4 * ne[i]);
-      if (rc) { delete h; return rc; }
+      if (rc) return rc;
       HIPCHK(hipMemcpy(h->lodv3[i].p, a.data(), a.size() * 4, hipMemcpyHostToDevice));
       HIPCHK(hipMemcpy(h->lodpl[i].p, b.data(), b.size() * 4, hipMemcpyHostToDevice));
       HIPCHK(hipMemcpy(h->lodei[i].p, le[i], 4 * ne[i] * sizeof(unsigned short), hipMemcpyHostToDevice));
@@ -2148,12 +2257,11 @@ int tcmp_create(int device, tcmp_handle** out) {
         for (int k = 0; k < 3; ++k)
           ev[4 * e + k] = (float)(lv[i][3 * le[i][4 * e + 1] + k] - lv[i][3 * le[i][4 * e] + k]);
       rc = h->lodev[i].ensure(ev.size());
-      if (rc) { delete h; return rc; }
+      if (rc) return rc;
       HIPCHK(hipMemcpy(h->lodev[i].p, ev.data(), ev.size() * 4, hipMemcpyHostToDevice));
     }
     // the links' inscribed spheres (box and mesh certificates in phase B)
-    rc = upload_spheres(h);
-    if (rc) { delete h; return rc; }
+    if ((rc = upload_spheres(h))) return rc;
     // dynamic LDS above 64 KiB per workgroup must be allowed explicitly
     const int lim = (int)stage_lds_bytes(kMaxObstacles);
     for (const void* k : {(const void*)k_edges<false, 1>, (const void*)k_edges<true, 1>,
@@ -2163,16 +2271,17 @@ int tcmp_create(int device, tcmp_handle** out) {
                           (const void*)k_debug_pair_pd<false>, (const void*)k_debug_pair_pd<true>,
                           (const void*)k_rewire_apply<false>, (const void*)k_rewire_apply<true>})
       HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-    if (int rc2 = fleet_lds_limits()) { delete h; return rc2; }
-    if (int rc2 = repair_lds_limits()) { delete h; return rc2; }
-    if (int rc2 = goal_lds_limits()) { delete h; return rc2; }
+    if ((rc = fleet_lds_limits())) return rc;
+    if ((rc = repair_lds_limits())) return rc;
+    if ((rc = goal_lds_limits())) return rc;
   }
-  HIPCHK(hipMalloc(&h->st, sizeof(DevState)));
+  rc = h->st.ensure();
+  rc = rc ? rc : h->pin_mem.ensure(sizeof(tcmp_handle::Pin));
+  rc = rc ? rc : h->st_nn.ensure();
+  rc = rc ? rc : h->dP.ensure();
+  rc = rc ? rc : h->dPx.ensure();
+  if (rc) return rc;
   HIPCHK(hipMemset(h->st, 0, sizeof(DevState)));
-  HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&h->pin), sizeof(tcmp_handle::Pin)));
-  HIPCHK(hipMalloc(&h->st_nn, sizeof(DevState)));
-  HIPCHK(hipMalloc(&h->dP, sizeof(PlanParams)));
-  HIPCHK(hipMalloc(&h->dPx, sizeof(PlanParams)));
   HIPCHK(hipMemset(h->st_nn, 0, sizeof(DevState)));
   if (const char* e = getenv("TCMP_NN_WAVES_PER_CU")) h->nn_waves_per_cu = std::max(1, atoi(e));
   if (const char* e = getenv("TCMP_GRAPHS")) h->use_graphs = atoi(e) != 0;
@@ -2185,7 +2294,7 @@ int tcmp_create(int device, tcmp_handle** out) {
   }
   if (const char* e = getenv("TCMP_EDGE_WPS")) h->edge_wps = std::max(1, std::min(2, atoi(e)));
   if (const char* e = getenv("TCMP_NN_CSORT")) h->nn_cand_count_bits = std::min(16, std::max(0, atoi(e)));
-  *out = h;
+  *out = owner.release();
   return 0;
 }
 
@@ -2193,106 +2302,8 @@ int tcmp_destroy(tcmp_handle* h) {
   if (!h) return 0;
   Entry entry;
   (void)hipSetDevice(h->device);
+  // nothing is freed under work still queued: this wait is what makes the destructor safe
   (void)hipStreamSynchronize(h->stream);
-  h->verts32.release();
-  h->planes32.release();
-  h->eidx.release();
-  h->geo_ev.release();
-  h->sph.release();
-  h->obs32.release();
-  h->t0tab.release();
-  h->mrange.release();
-  for (auto* b : {&h->mib, &h->mv64, &h->mp64, &h->me64, &h->base_geo, &h->base_pd}) b->release();
-  for (auto* b : {&h->mv32, &h->mp32, &h->me32, &h->mcl, &h->lcl[0], &h->lcl[1]}) b->release();
-  for (int i = 0; i < 2; ++i) {
-    for (auto* b : {&h->lv32[i], &h->lp32[i], &h->le32[i], &h->lodv3[i], &h->lodpl[i], &h->lodev[i]})
-      b->release();
-    h->lodei[i].release();
-  }
-  for (auto* b : {&h->verts, &h->planes, &h->edges, &h->obs, &h->cfg, &h->tgt, &h->cand,
-                  &h->last, &h->erec, &h->wp, &h->tq, &h->tqd, &h->tqdd, &h->tpsg, &h->ttau, &h->s0,
-                  &h->s1, &h->s2, &h->s3})
-    b->release();
-  for (auto* b : {&h->parent, &h->nn, &h->nsafe, &h->nsteps, &h->nbr, &h->ncount, &h->i0,
-                  &h->i1, &h->i2, &h->rwlist})
-    b->release();
-  h->nnscore.release();
-  h->f_desc.release();
-  h->f_off.release();
-  h->dpin.release();
-  if (h->dep_ev) (void)hipEventDestroy(h->dep_ev);
-  if (h->scene_ev) (void)hipEventDestroy(h->scene_ev);
-  if (h->scene_pin) (void)hipHostFree(h->scene_pin);
-  if (h->fetch_pin) (void)hipHostFree(h->fetch_pin);
-  for (auto* b : {&h->nkeys_in, &h->skeys, &h->ckeys_in, &h->ckeys}) b->release();
-  h->cs_hist.release();
-  h->cs_hoff.release();
-  for (auto* b : {&h->nvals_in, &h->svals, &h->cvals_in, &h->cperm}) b->release();
-  h->stree.release();
-  h->srow.release();
-  h->cbox.release();
-  h->cboxf.release();
-  h->sboxf.release();
-  h->bboxf.release();
-  h->chome.release();
-  h->cflag.release();
-  h->cid.release();
-  h->cstart.release();
-  h->sflag.release();
-  h->sid.release();
-  h->sstart.release();
-  h->ckey.release();
-  h->bcount.release();
-  h->boff.release();
-  h->sort_tmp.release();
-  h->meta.release();
-  h->cgoal.release();
-  h->second.release();
-  h->chain.release();
-  h->u0.release();
-  for (auto* b : {&h->sc_wp[0], &h->sc_wp[1], &h->sc_from, &h->sc_to, &h->sc_last, &h->sc_rec,
-                  &h->sc_len, &h->sc_orig})
-    b->release();
-  for (auto* b : {&h->sc_nsafe, &h->sc_nsteps}) b->release();
-  h->sc_kl.release();
-  h->sc_hops.release();
-  h->sc_stats.release();
-  if (h->st_sc) (void)hipFree(h->st_sc);
-  for (auto* b : {&h->rt_in[0], &h->rt_in[1], &h->rt_in[2], &h->rt_in[3], &h->rt_o[0], &h->rt_o[1],
-                  &h->rt_o[2], &h->rt_zero, &h->rt_g})
-    b->release();
-  h->rt_part.release();
-  for (auto* b : {&h->rp_wp, &h->rp_o[0], &h->rp_o[1], &h->rp_o[2]}) b->release();
-  for (auto* b : {&h->rp_gate[0], &h->rp_gate[1], &h->rp_dirty}) b->release();
-  h->rp_first.release();
-  h->rp_count.release();
-  h->rp_sum.release();
-  if (h->rp_pin) (void)hipHostFree(h->rp_pin);
-  h->pl_gate.release();
-  for (auto* b : {&h->rr_rows, &h->rr_part, &h->rr_tab}) b->release();
-  h->rr_off.release();
-  h->rr_org.release();
-  for (auto* b : {&h->pf_t[0], &h->pf_t[1], &h->pf_t[2], &h->pf_coef, &h->pf_hi, &h->pf_lo, &h->pf_x,
-                  &h->pf_u})
-    b->release();
-  h->pf_bad.release();
-  h->pf_off.release();
-  h->pf_ff.release();
-  h->pf_res.release();
-  for (auto* b : {&h->gs_pose, &h->gs_free, &h->gs_refw, &h->gs_xpose, &h->gs_xfree, &h->gs_sol,
-                  &h->gs_head, &h->gs_out})
-    b->release();
-  for (auto* b : {&h->gs_cnt, &h->gs_list, &h->gs_lid, &h->gs_oid}) b->release();
-  for (auto* b : {&h->gs_key, &h->gs_lkey, &h->gs_ctr}) b->release();
-  for (auto e : h->ev_rec) (void)hipEventDestroy(e);
-  h->drop_graph();
-  for (auto e : h->ev_pool) (void)hipEventDestroy(e);
-  if (h->st) (void)hipFree(h->st);
-  if (h->pin) (void)hipHostFree(h->pin);
-  if (h->st_nn) (void)hipFree(h->st_nn);
-  if (h->dP) (void)hipFree(h->dP);
-  if (h->dPx) (void)hipFree(h->dPx);
-  if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
   return 0;
 }
@@ -2492,25 +2503,16 @@ int upload_meshes(tcmp_handle* h) {
   for (int f = 0; f < F; ++f)
     for (int k = 0; k < 4; ++k) p64[4 * f + k] = planes[4 * f + k];
   std::vector<float> v32(v64.begin(), v64.end()), p32(p64.begin(), p64.end()), e32(e64.begin(), e64.end());
-  int rc = h->mrange.ensure(rg.size());
-  rc = rc ? rc : h->mib.ensure(ib.size());
-  rc = rc ? rc : h->mv64.ensure(v64.size());
-  rc = rc ? rc : h->mp64.ensure(p64.size());
-  rc = rc ? rc : h->me64.ensure(e64.size());
-  rc = rc ? rc : h->mv32.ensure(v32.size());
-  rc = rc ? rc : h->mp32.ensure(p32.size());
-  rc = rc ? rc : h->me32.ensure(e32.size());
-  rc = rc ? rc : h->mcl.ensure(mcl.size());
+  int rc = upload(h, h->mcl, mcl.data(), mcl.size());
+  rc = rc ? rc : upload(h, h->mrange, rg.data(), rg.size());
+  rc = rc ? rc : upload(h, h->mib, ib.data(), ib.size());
+  rc = rc ? rc : upload(h, h->mv64, v64.data(), v64.size());
+  rc = rc ? rc : upload(h, h->mp64, p64.data(), p64.size());
+  rc = rc ? rc : upload(h, h->me64, e64.data(), e64.size());
+  rc = rc ? rc : upload(h, h->mv32, v32.data(), v32.size());
+  rc = rc ? rc : upload(h, h->mp32, p32.data(), p32.size());
+  rc = rc ? rc : upload(h, h->me32, e32.data(), e32.size());
   if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(h->mcl.p, mcl.data(), mcl.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->mrange.p, rg.data(), rg.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->mib.p, ib.data(), ib.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->mv64.p, v64.data(), v64.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->mp64.p, p64.data(), p64.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->me64.p, e64.data(), e64.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->mv32.p, v32.data(), v32.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->mp32.p, p32.data(), p32.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->me32.p, e32.data(), e32.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
   if (int rc_s = sync_stream(h)) return rc_s;
   h->mrange_h = rg;
   if (int rc = upload_lods(h)) return rc;
@@ -2537,9 +2539,7 @@ int upload_spheres(tcmp_handle* h) {
     if (src)
       for (int i = 0; i < K * 4; ++i) a[(size_t)(TCMP_NLINKS + m) * K * 4 + i] = (float)src[i];
   }
-  int rc = h->sph.ensure(a.size());
-  if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(h->sph.p, a.data(), a.size() * 4, hipMemcpyHostToDevice, h->stream));
+  if (int rc = upload(h, h->sph, a.data(), a.size())) return rc;
   if (nm)
     HIPCHK(hipMemcpyAsync(h->mrange.p, rg.data(), rg.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
   if (int rc_s = sync_stream(h)) return rc_s;
@@ -2591,15 +2591,11 @@ int upload_lods(tcmp_handle* h) {
     std::vector<float> v32((size_t)V * 4, 0.f), p32(pl.begin(), pl.end()), e32(e64.begin(), e64.end());
     for (int r = 0; r < V; ++r)
       for (int k = 0; k < 3; ++k) v32[4 * r + k] = (float)v[3 * r + k];
-    int rc = h->lv32[i].ensure(v32.size());
-    rc = rc ? rc : h->lp32[i].ensure(p32.size());
-    rc = rc ? rc : h->le32[i].ensure(e32.size());
-    rc = rc ? rc : h->lcl[i].ensure(lcl.size());
+    int rc = upload(h, h->lcl[i], lcl.data(), lcl.size());
+    rc = rc ? rc : upload(h, h->lv32[i], v32.data(), v32.size());
+    rc = rc ? rc : upload(h, h->lp32[i], p32.data(), p32.size());
+    rc = rc ? rc : upload(h, h->le32[i], e32.data(), e32.size());
     if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(h->lcl[i].p, lcl.data(), lcl.size() * 4, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->lv32[i].p, v32.data(), v32.size() * 4, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->lp32[i].p, p32.data(), p32.size() * 4, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->le32[i].p, e32.data(), e32.size() * 4, hipMemcpyHostToDevice, h->stream));
     if (int rc_s = sync_stream(h)) return rc_s;  // host staging buffers go out of scope
     for (int m = 0; m < nm; ++m) {
       // LOD hull m belongs to mesh m (user) or to link mesh h->n_mesh + (m - n_user)
@@ -2718,16 +2714,10 @@ int upload_scene(tcmp_handle* h) {
   // previous scene's copies have been done
   const size_t b64 = tmp.size() * sizeof(double), b32 = t32.size() * sizeof(float),
                bt0 = t0.size() * sizeof(unsigned);
-  if (h->scene_ev) HIPCHK(hipEventSynchronize(h->scene_ev));
-  else HIPCHK(hipEventCreateWithFlags(&h->scene_ev, hipEventDisableTiming));
-  if (h->scene_pin_n < b64 + b32 + bt0) {
-    if (h->scene_pin) HIPCHK(hipHostFree(h->scene_pin));
-    h->scene_pin = nullptr;
-    h->scene_pin_n = 0;
-    HIPCHK(hipHostMalloc(&h->scene_pin, b64 + b32 + bt0));
-    h->scene_pin_n = b64 + b32 + bt0;
-  }
-  unsigned char* pin = static_cast<unsigned char*>(h->scene_pin);
+  if (h->scene_ev.e) HIPCHK(hipEventSynchronize(h->scene_ev.e));
+  else if (int rc = h->scene_ev.ensure(hipEventDisableTiming)) return rc;
+  if (int rc = h->scene_pin.ensure(b64 + b32 + bt0)) return rc;
+  unsigned char* pin = static_cast<unsigned char*>(h->scene_pin.p);
   memcpy(pin, tmp.data(), b64);
   memcpy(pin + b64, t32.data(), b32);
   HIPCHK(hipMemcpyAsync(h->obs.p, pin, b64, hipMemcpyHostToDevice, h->stream));
@@ -2737,7 +2727,7 @@ int upload_scene(tcmp_handle* h) {
     HIPCHK(hipMemcpyAsync(h->t0tab.p, pin + b64 + b32, bt0, hipMemcpyHostToDevice, h->stream));
   }
   h->t0tab_ok = tabs;
-  HIPCHK(hipEventRecord(h->scene_ev, h->stream));
+  HIPCHK(hipEventRecord(h->scene_ev.e, h->stream));
   h->n_obs = n;
   return 0;
 }
@@ -2805,25 +2795,16 @@ int tcmp_set_meshes(tcmp_handle* h, const double* verts, const int32_t* vert_off
                     const int32_t* edge_off, const double* boxes, int32_t n_mesh) {
   TCMP_ENTER(h);
   if (n_mesh < 0) return fail(-1, "bad mesh count");
-  if (n_mesh > 0 && (!verts || !vert_off || !planes || !plane_off || !edges || !edge_off || !boxes))
-    return fail(-1, "null mesh array");
+  if (n_mesh > 0 && !boxes) return fail(-1, "null mesh box array");
   if (h->n_box + n_mesh > kMaxObstacles)
     return fail(-1, "too many obstacles (" + std::to_string(h->n_box + n_mesh) + " > " +
                         std::to_string(kMaxObstacles) + ", the LDS-staged scene limit)");
+  const tcmp_hulls H{verts, vert_off, planes, plane_off, edges, edge_off};
+  if (n_mesh > 0)
+    if (int rc = check_hulls(&H, n_mesh, "mesh")) return rc;
   const int V = n_mesh ? vert_off[n_mesh] : 0, F = n_mesh ? plane_off[n_mesh] : 0,
             E = n_mesh ? edge_off[n_mesh] : 0;
-  if (n_mesh && (vert_off[0] != 0 || plane_off[0] != 0 || edge_off[0] != 0))
-    return fail(-1, "mesh offsets must start at 0");
   for (int m = 0; m < n_mesh; ++m) {
-    const int nv = vert_off[m + 1] - vert_off[m], nf = plane_off[m + 1] - plane_off[m],
-              ne = edge_off[m + 1] - edge_off[m];
-    if (nv < 4 || nf < 4 || ne < 6) return fail(-1, "mesh " + std::to_string(m) + " is not a 3-D hull");
-    for (int e = edge_off[m]; e < edge_off[m + 1]; ++e) {
-      const int* q = edges + 4 * e;
-      if (q[0] < 0 || q[0] >= nv || q[1] < 0 || q[1] >= nv || q[2] < 0 || q[2] >= nf || q[3] < 0 ||
-          q[3] >= nf)
-        return fail(-1, "mesh " + std::to_string(m) + ": edge index out of range");
-    }
     const double* b = boxes + 18 * m;
     for (int k = 12; k < 18; ++k)
       if (!(b[k] >= 0)) return fail(-1, "mesh " + std::to_string(m) + ": negative box half extent");
@@ -2924,10 +2905,8 @@ int tcmp_rne_batch(tcmp_handle* h, const double* q, const double* qd, const doub
   hipLaunchKernelGGL(k_rne, dim3(grid_for(n, 128)), dim3(128), 0, h->stream, h->s0.p, h->s1.p,
                      h->s2.p, (long long)n, payload_mass, h->s3.p);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(tau, h->s3.p, (size_t)n * 7 * sizeof(double), hipMemcpyDeviceToHost,
-                        h->stream));
-  if (int rc_s = sync_stream(h)) return rc_s;
-  return 0;
+  if (int rc = download(h, tau, h->s3.p, (size_t)n * 7)) return rc;
+  return sync_stream(h);
 }
 
 int tcmp_ik(tcmp_handle* h, const double* poses, const double* free_q7, int64_t n, double* sols,
@@ -2936,42 +2915,31 @@ int tcmp_ik(tcmp_handle* h, const double* poses, const double* free_q7, int64_t 
   if (n < 0 || (n > 0 && (!poses || !free_q7 || !sols || !count)))
     return fail(-1, "bad arguments");
   if (n == 0) return 0;
-  int rc = h->s0.ensure((size_t)n * 12);
-  rc = rc ? rc : h->s1.ensure((size_t)n);
-  rc = rc ? rc : h->s2.ensure((size_t)n * 56);
+  int rc = h->s2.ensure((size_t)n * 56);
   rc = rc ? rc : h->i0.ensure((size_t)n);
+  rc = rc ? rc : upload(h, h->s0, poses, (size_t)n * 12);
+  rc = rc ? rc : upload(h, h->s1, free_q7, (size_t)n);
   if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(h->s0.p, poses, (size_t)n * 12 * sizeof(double), hipMemcpyHostToDevice,
-                        h->stream));
-  HIPCHK(hipMemcpyAsync(h->s1.p, free_q7, (size_t)n * sizeof(double), hipMemcpyHostToDevice,
-                        h->stream));
   hipLaunchKernelGGL(k_ik, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, h->s0.p, h->s1.p,
                      (long long)n, h->s2.p, h->i0.p);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(sols, h->s2.p, (size_t)n * 56 * sizeof(double), hipMemcpyDeviceToHost,
-                        h->stream));
-  HIPCHK(hipMemcpyAsync(count, h->i0.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost,
-                        h->stream));
-  if (int rc_s = sync_stream(h)) return rc_s;
-  return 0;
+  if (int rc = download(h, sols, h->s2.p, (size_t)n * 56)) return rc;
+  if (int rc = download(h, count, h->i0.p, (size_t)n)) return rc;
+  return sync_stream(h);
 }
 
 int tcmp_fk(tcmp_handle* h, const double* q, int64_t n, double* poses) {
   TCMP_ENTER(h);
   if (n < 0 || (n > 0 && (!q || !poses))) return fail(-1, "bad arguments");
   if (n == 0) return 0;
-  int rc = h->s0.ensure((size_t)n * 7);
-  rc = rc ? rc : h->s1.ensure((size_t)n * 12);
+  int rc = h->s1.ensure((size_t)n * 12);
+  rc = rc ? rc : upload(h, h->s0, q, (size_t)n * 7);
   if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(h->s0.p, q, (size_t)n * 7 * sizeof(double), hipMemcpyHostToDevice,
-                        h->stream));
   hipLaunchKernelGGL(k_fk8, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, h->s0.p,
                      (long long)n, h->s1.p);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(poses, h->s1.p, (size_t)n * 12 * sizeof(double), hipMemcpyDeviceToHost,
-                        h->stream));
-  if (int rc_s = sync_stream(h)) return rc_s;
-  return 0;
+  if (int rc = download(h, poses, h->s1.p, (size_t)n * 12)) return rc;
+  return sync_stream(h);
 }
 
 int tcmp_torque_ok(tcmp_handle* h, const double* q, const double* qd, const double* qdd,
@@ -2989,9 +2957,8 @@ int tcmp_torque_ok(tcmp_handle* h, const double* q, const double* qd, const doub
                      h->stream, h->s0.p, qd ? h->s1.p : nullptr, qdd ? h->s2.p : nullptr,
                      (long long)n, payload_mass, h->i0.p);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(ok, h->i0.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  if (int rc_s = sync_stream(h)) return rc_s;
-  return 0;
+  if (int rc = download(h, ok, h->i0.p, (size_t)n)) return rc;
+  return sync_stream(h);
 }
 
 int tcmp_check_configs(tcmp_handle* h, const double* q, int64_t n, int32_t* collides) {
@@ -3004,10 +2971,8 @@ int tcmp_check_configs(tcmp_handle* h, const double* q, int64_t n, int32_t* coll
   hipLaunchKernelGGL(h->mesh_kernels() ? k_check_configs<true> : k_check_configs<false>, dim3(grid_for(n, 256)), dim3(256), lds_bytes(h), h->stream, h->s0.p,
                      (long long)n, h->scene(), h->geo(), h->i0.p, 0);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(collides, h->i0.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost,
-                        h->stream));
-  if (int rc_s = sync_stream(h)) return rc_s;
-  return 0;
+  if (int rc = download(h, collides, h->i0.p, (size_t)n)) return rc;
+  return sync_stream(h);
 }
 
 // panda_link0 against every obstacle of the scene (boxes, then user meshes) into h->base_pd
@@ -3046,10 +3011,8 @@ int tcmp_base_pd(tcmp_handle* h, double* pd, int32_t n) {
   if (n == 0) return 0;
   if (!pd) return fail(-1, "bad arguments");
   if (int rc = launch_base_pd(h)) return rc;
-  HIPCHK(hipMemcpyAsync(pd, h->base_pd.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost,
-                        h->stream));
-  if (int rc_s = sync_stream(h)) return rc_s;
-  return 0;
+  if (int rc = download(h, pd, h->base_pd.p, (size_t)n)) return rc;
+  return sync_stream(h);
 }
 
 int tcmp_debug_pair_pd(tcmp_handle* h, const int32_t* link, const double* pose,
@@ -3088,26 +3051,20 @@ int tcmp_debug_pair_pd(tcmp_handle* h, const int32_t* link, const double* pose,
     if ((flags & kDbgInnerBox) && !(h->mesh_box[18 * (size_t)m + 15] > 0.0))
       return fail(-1, "the mesh has no inner box");
   }
-  int rc = h->s0.ensure((size_t)n * 12);
-  rc = rc ? rc : h->s1.ensure((size_t)n);
-  rc = rc ? rc : h->i0.ensure((size_t)n);
-  rc = rc ? rc : h->i1.ensure((size_t)n);
+  int rc = h->s1.ensure((size_t)n);
   rc = rc ? rc : h->i2.ensure((size_t)n);
+  rc = rc ? rc : upload(h, h->s0, pose, (size_t)n * 12);
+  rc = rc ? rc : upload(h, h->i0, link, (size_t)n);
+  rc = rc ? rc : upload(h, h->i1, obstacle, (size_t)n);
   if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(h->s0.p, pose, (size_t)n * 12 * sizeof(double), hipMemcpyHostToDevice,
-                        h->stream));
-  HIPCHK(hipMemcpyAsync(h->i0.p, link, (size_t)n * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->i1.p, obstacle, (size_t)n * sizeof(int), hipMemcpyHostToDevice,
-                        h->stream));
   hipLaunchKernelGGL(h->mesh_kernels() ? k_debug_pair_pd<true> : k_debug_pair_pd<false>,
                      dim3(grid_for(n, 4)), dim3(256), lds_bytes(h), h->stream, h->i0.p, h->s0.p,
                      h->i1.p, (int)n, (int)stage, (int)flags, h->scene(), h->geo(), h->s1.p,
                      h->i2.p);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(pd, h->s1.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipMemcpyAsync(info, h->i2.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  if (int rc_s = sync_stream(h)) return rc_s;
-  return 0;
+  if (int rc = download(h, pd, h->s1.p, (size_t)n)) return rc;
+  if (int rc = download(h, info, h->i2.p, (size_t)n)) return rc;
+  return sync_stream(h);
 }
 
 int tcmp_debug_wave_reduce(tcmp_handle* h, const float* values, int64_t n, float* out) {
@@ -3125,10 +3082,8 @@ int tcmp_debug_wave_reduce(tcmp_handle* h, const float* values, int64_t n, float
   hipLaunchKernelGGL(k_debug_wave_reduce, dim3(grid_for(n, 4)), dim3(256), 0, h->stream, in_d,
                      (int)n, out_d);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(out, out_d, (size_t)n * 9 * sizeof(float), hipMemcpyDeviceToHost,
-                        h->stream));
-  if (int rc_s = sync_stream(h)) return rc_s;
-  return 0;
+  if (int rc = download(h, out, out_d, (size_t)n * 9)) return rc;
+  return sync_stream(h);
 }
 
 int tcmp_gauss_clusters(const tcmp_hulls* H, int32_t n, double* records, float* cones,
@@ -3172,10 +3127,8 @@ int tcmp_check_body(tcmp_handle* h, const double* q, int64_t n, int32_t* collide
                        (long long)n, h->base_pd.p, nb);
     HIPCHK(hipGetLastError());
   }
-  HIPCHK(hipMemcpyAsync(collides, h->i0.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost,
-                        h->stream));
-  if (int rc_s = sync_stream(h)) return rc_s;
-  return 0;
+  if (int rc = download(h, collides, h->i0.p, (size_t)n)) return rc;
+  return sync_stream(h);
 }
 
 int tcmp_check_edges(tcmp_handle* h, const double* from, const double* to, int64_t n,
@@ -3201,12 +3154,11 @@ int tcmp_check_edges(tcmp_handle* h, const double* from, const double* to, int64
   EdgeJob J{h->s0.p, nullptr, h->s1.p, (int)n, h->i0.p, h->i1.p, h->s2.p, nullptr, nullptr,
             h->erec.p};
   HIPCHK(hipMemcpyAsync(h->dPx, &P, sizeof(P), hipMemcpyHostToDevice, h->stream));
-  if ((rc = launch_edges(h, J, h->dPx))) return rc;
+  if ((rc = launch_edges(h, h->st, J, h->dPx))) return rc;
   std::vector<double> tmp((size_t)n * 8);
-  HIPCHK(hipMemcpyAsync(n_safe, h->i0.p, n * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipMemcpyAsync(n_steps, h->i1.p, n * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipMemcpyAsync(tmp.data(), h->s2.p, tmp.size() * sizeof(double), hipMemcpyDeviceToHost,
-                        h->stream));
+  if (int rc = download(h, n_safe, h->i0.p, n)) return rc;
+  if (int rc = download(h, n_steps, h->i1.p, n)) return rc;
+  if (int rc = download(h, tmp.data(), h->s2.p, tmp.size())) return rc;
   if (int rc_s = sync_stream(h)) return rc_s;
   for (long long i = 0; i < n; ++i)
     for (int k = 0; k < 7; ++k) last[7 * i + k] = tmp[8 * i + k];
@@ -3255,7 +3207,7 @@ int tcmp_nearest(tcmp_handle* h, const double* tree, int64_t T, const double* sa
   rc = launch_nearest(h, P, h->dPx, h->st_nn, h->s0.p, T, h->s1.p, (int)n, h->i0.p, h->s2.p,
                       nullptr);
   if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(idx, h->i0.p, n * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  if (int rc = download(h, idx, h->i0.p, n)) return rc;
   if (int rc_s = sync_stream(h)) return rc_s;
   // the scan's timing events belong to no plan
   h->ev_used.resize(ev_before);
@@ -3274,21 +3226,18 @@ int tcmp_minjerk(tcmp_handle* h, const double* waypoints, int64_t n_wp, int64_t 
   const long long K = (n_wp - 1) * ni;
   if (K == 0) return 0;
   if (!q || !qd || !qdd) return fail(-1, "bad arguments");
-  int rc = h->s0.ensure((size_t)n_wp * 7);
-  rc = rc ? rc : h->s1.ensure((size_t)K * 7);
+  int rc = h->s1.ensure((size_t)K * 7);
   rc = rc ? rc : h->s2.ensure((size_t)K * 7);
   rc = rc ? rc : h->s3.ensure((size_t)K * 7);
+  rc = rc ? rc : upload(h, h->s0, waypoints, (size_t)n_wp * 7);
   if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(h->s0.p, waypoints, n_wp * 7 * sizeof(double), hipMemcpyHostToDevice,
-                        h->stream));
   hipLaunchKernelGGL(k_minjerk, dim3(std::min<unsigned>(grid_for(K, 256), 4096)), dim3(256), 0,
                      h->stream, h->s0.p, (long long)n_wp, (long long)ni, h->s1.p, h->s2.p, h->s3.p);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(q, h->s1.p, K * 7 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipMemcpyAsync(qd, h->s2.p, K * 7 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipMemcpyAsync(qdd, h->s3.p, K * 7 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (int rc_s = sync_stream(h)) return rc_s;
-  return 0;
+  if (int rc = download(h, q, h->s1.p, K * 7)) return rc;
+  if (int rc = download(h, qd, h->s2.p, K * 7)) return rc;
+  if (int rc = download(h, qdd, h->s3.p, K * 7)) return rc;
+  return sync_stream(h);
 }
 
 int tcmp_validate_traj(tcmp_handle* h, const double* q, const double* qd, const double* qdd,
@@ -3318,7 +3267,7 @@ int tcmp_validate_traj(tcmp_handle* h, const double* q, const double* qd, const 
   unsigned long long ff = 0;
   HIPCHK(hipMemcpyAsync(&ff, h->u0.p, sizeof(ff), hipMemcpyDeviceToHost, h->stream));
   if (tau)
-    HIPCHK(hipMemcpyAsync(tau, h->s3.p, n * 7 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (int rc = download(h, tau, h->s3.p, n * 7)) return rc;
   if (int rc_s = sync_stream(h)) return rc_s;
   *first_fail = ff == ~0ull ? -1 : (int64_t)ff;
   return 0;
@@ -3422,14 +3371,7 @@ int plan_begin_launch(tcmp_handle* h, const tcmp_plan_cfg* cfg, tcmp_plan_result
     rc = rc ? rc : h->tpsg.ensure((size_t)h->kcap);
     rc = rc ? rc : h->ttau.ensure((size_t)h->kcap * 7);
     // (grown only when a larger execution time raises kcap: the first plan of an engine)
-    const size_t fb = (size_t)h->kcap * 29 * sizeof(double);
-    if (!rc && h->fetch_pin_n < fb) {
-      if (h->fetch_pin) HIPCHK(hipHostFree(h->fetch_pin));
-      h->fetch_pin = nullptr;
-      h->fetch_pin_n = 0;
-      HIPCHK(hipHostMalloc(&h->fetch_pin, fb));
-      h->fetch_pin_n = fb;
-    }
+    rc = rc ? rc : h->fetch_pin.ensure((size_t)h->kcap * 29 * sizeof(double));
     rc = rc ? rc : h->s0.ensure(16);
     rc = rc ? rc : h->i0.ensure(2);
     if (rc) return rc;
@@ -3443,7 +3385,7 @@ int plan_begin_launch(tcmp_handle* h, const tcmp_plan_cfg* cfg, tcmp_plan_result
   // one upload and one host wait: the handle's pinned block holds the start / goal rows, the
   // root, the plan state and parameters; k_plan_init scatters them on the device
   if (int rc2 = h->dpin.ensure(sizeof(tcmp_handle::Pin))) return rc2;
-  tcmp_handle::Pin& pn = *h->pin;
+  tcmp_handle::Pin& pn = *h->pin();
   memset(pn.sg, 0, sizeof(pn.sg));
   memcpy(pn.sg, cfg->start, sizeof(double) * 7);
   memcpy(pn.sg + 8, cfg->goal, sizeof(double) * 7);
@@ -3472,7 +3414,7 @@ int plan_begin_launch(tcmp_handle* h, const tcmp_plan_cfg* cfg, tcmp_plan_result
 }
 
 int plan_begin_complete(tcmp_handle* h, tcmp_plan_result* result) {
-  tcmp_handle::Pin& pn = *h->pin;
+  tcmp_handle::Pin& pn = *h->pin();
   if (int rc_s = sync_stream(h)) return rc_s;
   h->plan_open = true;
   result->n_nodes = 1;
@@ -3646,7 +3588,7 @@ static int round_search(tcmp_handle* h, bool device_samples, int32_t nb, long lo
   // first kernel); the scan turns them into the insertion offsets
   J.accepted = h->bcount.p;
   hipEvent_t ek = nullptr;
-  if (int rc = launch_edges(h, J, h->dP, false, &ek)) return rc;
+  if (int rc = launch_edges(h, h->st, J, h->dP, false, &ek)) return rc;
   h->span(F_EDGE_PREP, e1, ek);
   h->ins_ev = h->mark_end(F_EDGES, ek);
   hipLaunchKernelGGL(k_ins_scan, dim3(1), dim3(1024), 0, h->stream, h->st, h->bcount.p, nblk,
@@ -3720,8 +3662,7 @@ static inline long long sr_lo(long long B, int q, int W) { return B * q / W; }
 // a host-side copy of the tree size, advanced like k_ins_final does
 static int sr_tree_size(tcmp_handle* h, long long* T) {
   HIPCHK(hipMemcpyAsync(T, &h->st->n_nodes, sizeof(*T), hipMemcpyDeviceToHost, h->stream));
-  if (int rc_s = sync_stream(h)) return rc_s;
-  return 0;
+  return sync_stream(h);
 }
 
 static int sr_check(tcmp_handle* h, long long n_samples, int batch, int world) {
@@ -4092,11 +4033,11 @@ static int plan_finish_launch(tcmp_handle* h, tcmp_plan_result* r, bool traj) {
   if (traj) finish_launch_traj(h);
   HIPCHK(hipGetLastError());
   h->mark_end(F_FINISH, e0);
-  HIPCHK(hipMemcpyAsync(&h->pin->st, h->st, sizeof(DevState), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(&h->pin()->st, h->st, sizeof(DevState), hipMemcpyDeviceToHost, h->stream));
   return 0;
 }
 static int plan_finish_complete(tcmp_handle* h, tcmp_plan_result* r, bool traj) {
-  DevState& s = h->pin->st;
+  DevState& s = h->pin()->st;
   if (int rc_s = sync_stream(h)) return rc_s;
   r->goal_node = s.goal_node;
   if (s.overflow == 1) return fail(-3, "tree capacity exceeded");
@@ -4198,15 +4139,15 @@ int tcmp_plan_fetch(tcmp_handle* h, double* waypoints, double* q, double* qd, do
   if (h->fin_W == 0) return fail(-1, "no plan to fetch");
   const long long W = (long long)h->fin_W, K = (long long)h->fin_K;
   if (waypoints && W)
-    HIPCHK(hipMemcpyAsync(waypoints, h->wp.p, W * 7 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (K && (size_t)K * 29 * sizeof(double) <= h->fetch_pin_n) {
+    if (int rc = download(h, waypoints, h->wp.p, W * 7)) return rc;
+  if (K && (size_t)K * 29 * sizeof(double) <= h->fetch_pin.n) {
     // the trajectory rows through the pinned staging: one DMA per array, one host wait, then
     // host copies into the caller's arrays
     struct Part { double* dst; const double* src; size_t n; };
     const Part parts[5] = {{q, h->tq.p, (size_t)K * 7}, {qd, h->tqd.p, (size_t)K * 7},
                            {qdd, h->tqdd.p, (size_t)K * 7}, {psg, h->tpsg.p, (size_t)K},
                            {tau, h->ttau.p, (size_t)K * 7}};
-    double* pin = static_cast<double*>(h->fetch_pin);
+    double* pin = static_cast<double*>(h->fetch_pin.p);
     size_t off = 0;
     for (const Part& p : parts) {
       if (p.dst) HIPCHK(hipMemcpyAsync(pin + off, p.src, p.n * sizeof(double),
@@ -4228,32 +4169,31 @@ int tcmp_plan_fetch(tcmp_handle* h, double* waypoints, double* q, double* qd, do
     if (psg) HIPCHK(hipMemcpyAsync(psg, h->tpsg.p, K * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (tau) HIPCHK(hipMemcpyAsync(tau, h->ttau.p, K * 7 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   }
-  if (int rc_s = sync_stream(h)) return rc_s;
-  return 0;
+  return sync_stream(h);
 }
 
 int tcmp_microbench(tcmp_handle* h, double* out) {
   TCMP_ENTER(h);
   if (!out) return fail(-1, "null out");
   // best of 5 launches each, HIP events on the handle's stream
-  hipEvent_t a, b;
-  HIPCHK(hipEventCreate(&a));
-  HIPCHK(hipEventCreate(&b));
+  Event a, b;
+  int rc = a.ensure(hipEventDefault);
+  rc = rc ? rc : b.ensure(hipEventDefault);
+  rc = rc ? rc : h->s0.ensure(4 * 65536);
+  if (rc) return rc;
   auto best_ms = [&](auto launch) -> double {
     double best = 1e30;
     for (int r = 0; r < 6; ++r) {
-      (void)hipEventRecord(a, h->stream);
+      (void)hipEventRecord(a.e, h->stream);
       launch();
-      (void)hipEventRecord(b, h->stream);
-      (void)hipEventSynchronize(b);
+      (void)hipEventRecord(b.e, h->stream);
+      (void)hipEventSynchronize(b.e);
       float ms = 0;
-      (void)hipEventElapsedTime(&ms, a, b);
+      (void)hipEventElapsedTime(&ms, a.e, b.e);
       if (r > 0) best = std::min(best, (double)ms);  // the first launch warms up
     }
     return best;
   };
-  int rc = h->s0.ensure(4 * 65536);
-  if (rc) return rc;
   const int blocks = std::max(1, h->cu_count) * 8, iters = 4096;
   const double threads = (double)blocks * 256;
   double ms = best_ms([&] {
@@ -4266,12 +4206,12 @@ int tcmp_microbench(tcmp_handle* h, double* out) {
   out[1] = 4.0 * kMbAcc * iters * threads / (ms * 1e-3) / 1e12;
   // HBM: 1 GiB float4 copy (2 GiB moved per launch), far past the caches
   const size_t n4 = ((size_t)1 << 30) / 16;
-  float4 *src = nullptr, *dst = nullptr;
-  HIPCHK(hipMalloc(&src, n4 * 16));
-  if (hipMalloc(&dst, n4 * 16) != hipSuccess) {
-    (void)hipFree(src);
-    return fail(-2, "microbench: hipMalloc");
-  }
+  // (freed at every return: each best_ms has waited for its last launch by then)
+  DBuf<float4> src_buf, dst_buf;
+  rc = src_buf.ensure(n4);
+  rc = rc ? rc : dst_buf.ensure(n4);
+  if (rc) return rc;
+  float4 *const src = src_buf.p, *const dst = dst_buf.p;
   (void)hipMemsetAsync(src, 0, n4 * 16, h->stream);
   ms = best_ms([&] {
     hipLaunchKernelGGL(k_mb_copy<4>, dim3((unsigned)(n4 / (256 * 4))), dim3(256), 0, h->stream,
@@ -4304,10 +4244,6 @@ int tcmp_microbench(tcmp_handle* h, double* out) {
   ms = best1;
   out[2] = 2.0 * (double)n4 * 16 / (ms * 1e-3) / 1e9;
   out[3] = (double)var;
-  (void)hipFree(src);
-  (void)hipFree(dst);
-  (void)hipEventDestroy(a);
-  (void)hipEventDestroy(b);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -4343,10 +4279,9 @@ int tcmp_plan_tree(tcmp_handle* h, int64_t cap, double* cfg, double* cost, int32
   const long long m = std::min<long long>(nn, cap);
   if (m <= 0) return 0;
   std::vector<double> tmp((size_t)m * 8);
-  HIPCHK(hipMemcpyAsync(tmp.data(), h->cfg.p, tmp.size() * sizeof(double), hipMemcpyDeviceToHost,
-                        h->stream));
+  if (int rc = download(h, tmp.data(), h->cfg.p, tmp.size())) return rc;
   if (parent)
-    HIPCHK(hipMemcpyAsync(parent, h->parent.p, m * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    if (int rc = download(h, parent, h->parent.p, m)) return rc;
   if (int rc_s = sync_stream(h)) return rc_s;
   for (long long i = 0; i < m; ++i) {
     if (cfg)
@@ -4378,9 +4313,8 @@ int tcmp_plan_debug_round(tcmp_handle* h, int64_t cap, double* cand, int32_t* nn
   }
   if (nn) HIPCHK(hipMemcpyAsync(nn, h->nn.p, m * sizeof(int), hipMemcpyDeviceToHost, h->stream));
   if (score)
-    HIPCHK(hipMemcpyAsync(score, h->nnscore.p, m * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (int rc_s = sync_stream(h)) return rc_s;
-  return 0;
+    if (int rc = download(h, score, h->nnscore.p, m)) return rc;
+  return sync_stream(h);
 }
 
 }  // extern "C"

@@ -892,9 +892,9 @@ int tcmp_plan_run_fused(tcmp_handle* const* hs, int32_t n, int64_t n_samples, in
   // fleet_lds_limits)
   // the other engines' queued work (their plan_begin) comes first; they wait for the rounds
   for (int q = 1; q < n; ++q) {
-    if (!hs[q]->dep_ev) HIPCHK(hipEventCreateWithFlags(&hs[q]->dep_ev, hipEventDisableTiming));
-    HIPCHK(hipEventRecord(hs[q]->dep_ev, hs[q]->stream));
-    HIPCHK(hipStreamWaitEvent(h->stream, hs[q]->dep_ev, 0));
+    if (int rc = hs[q]->dep_ev.ensure(hipEventDisableTiming)) return rc;
+    HIPCHK(hipEventRecord(hs[q]->dep_ev.e, hs[q]->stream));
+    HIPCHK(hipStreamWaitEvent(h->stream, hs[q]->dep_ev.e, 0));
   }
   int rounds = 0, scans = 0;
   long long base = h->samples_issued;
@@ -906,12 +906,12 @@ int tcmp_plan_run_fused(tcmp_handle* const* hs, int32_t n, int64_t n_samples, in
     base += nb;
     left -= nb;
   }
-  if (!h->dep_ev) HIPCHK(hipEventCreateWithFlags(&h->dep_ev, hipEventDisableTiming));
-  HIPCHK(hipEventRecord(h->dep_ev, h->stream));
+  if (int rc = h->dep_ev.ensure(hipEventDisableTiming)) return rc;
+  HIPCHK(hipEventRecord(h->dep_ev.e, h->stream));
   const int last_nb = (int)(n_samples % batch ? n_samples % batch : batch);
   for (int q = 0; q < n; ++q) {
     tcmp_handle* e = hs[q];
-    if (q) HIPCHK(hipStreamWaitEvent(e->stream, h->dep_ev, 0));
+    if (q) HIPCHK(hipStreamWaitEvent(e->stream, h->dep_ev.e, 0));
     e->samples_issued += n_samples;
     e->launches_nearest += rounds;
     e->launches_scan += scans;

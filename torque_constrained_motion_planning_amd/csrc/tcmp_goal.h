@@ -316,10 +316,7 @@ int tcmp_goal_search(tcmp_handle* h, const double* poses, int32_t n_pose, const 
   if (torque_mode < 0 || torque_mode > 3) return fail(-1, "unknown torque mode");
   const long long N = (long long)n_pose * n_free, NS = N * 8, R = (long long)n_pose * max_out;
   const int S = n_free * 8;
-  int rc = h->gs_pose.ensure((size_t)n_pose * 12);
-  rc = rc ? rc : h->gs_free.ensure((size_t)n_free);
-  rc = rc ? rc : h->gs_refw.ensure(14);
-  rc = rc ? rc : h->gs_xpose.ensure((size_t)N * 12);
+  int rc = h->gs_xpose.ensure((size_t)N * 12);
   rc = rc ? rc : h->gs_xfree.ensure((size_t)N);
   rc = rc ? rc : h->gs_sol.ensure((size_t)N * 56);
   rc = rc ? rc : h->gs_cnt.ensure((size_t)N);
@@ -342,12 +339,10 @@ int tcmp_goal_search(tcmp_handle* h, const double* poses, int32_t n_pose, const 
   double* const oq = h->gs_out.p;
   double* const od = oq + 7 * R;
   double* const oh = od + R;
-  HIPCHK(hipMemcpyAsync(h->gs_pose.p, poses, (size_t)n_pose * 12 * sizeof(double),
-                        hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->gs_free.p, free_q7, (size_t)n_free * sizeof(double),
-                        hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->gs_refw.p, refw, 14 * sizeof(double), hipMemcpyHostToDevice,
-                        h->stream));
+  rc = upload(h, h->gs_pose, poses, (size_t)n_pose * 12);
+  rc = rc ? rc : upload(h, h->gs_free, free_q7, (size_t)n_free);
+  rc = rc ? rc : upload(h, h->gs_refw, refw, 14);
+  if (rc) return rc;
   StageSpan t(h);
   HIPCHK(hipMemsetAsync(ctl, 0, (2 + 4 * (size_t)n_pose) * sizeof(unsigned long long), h->stream));
   HIPCHK(hipMemsetAsync(oq, 0, (size_t)R * 9 * sizeof(double), h->stream));
@@ -372,20 +367,15 @@ int tcmp_goal_search(tcmp_handle* h, const double* poses, int32_t n_pose, const 
   HIPCHK(hipGetLastError());
   t.end();
   std::vector<unsigned long long> hc(2 + 4 * (size_t)n_pose);
-  HIPCHK(hipMemcpyAsync(hc.data(), ctl, hc.size() * sizeof(unsigned long long),
-                        hipMemcpyDeviceToHost, h->stream));
+  if (int rc = download(h, hc.data(), ctl, hc.size())) return rc;
   if (q_out)
-    HIPCHK(hipMemcpyAsync(q_out, oq, (size_t)R * 7 * sizeof(double), hipMemcpyDeviceToHost,
-                          h->stream));
+    if (int rc = download(h, q_out, oq, (size_t)R * 7)) return rc;
   if (dist_out)
-    HIPCHK(hipMemcpyAsync(dist_out, od, (size_t)R * sizeof(double), hipMemcpyDeviceToHost,
-                          h->stream));
+    if (int rc = download(h, dist_out, od, (size_t)R)) return rc;
   if (headroom_out)
-    HIPCHK(hipMemcpyAsync(headroom_out, oh, (size_t)R * sizeof(double), hipMemcpyDeviceToHost,
-                          h->stream));
+    if (int rc = download(h, headroom_out, oh, (size_t)R)) return rc;
   if (id_out)
-    HIPCHK(hipMemcpyAsync(id_out, h->gs_oid.p, (size_t)R * sizeof(int), hipMemcpyDeviceToHost,
-                          h->stream));
+    if (int rc = download(h, id_out, h->gs_oid.p, (size_t)R)) return rc;
   if (int rc_s = sync_stream(h)) return rc_s;
   const float span = t.ms();
   if (ms) *ms = span;

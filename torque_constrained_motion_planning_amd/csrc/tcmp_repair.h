@@ -202,9 +202,9 @@ int rp_passes(tcmp_handle* h, const double* wp, long long W, long long ni, int m
   rc = rc ? rc : h->rp_count.ensure((size_t)nseg);
   rc = rc ? rc : h->rp_sum.ensure(sizeof(RpSum));
   if (rc) return rc;
-  if (!h->rp_pin) HIPCHK(hipHostMalloc(&h->rp_pin, sizeof(RpSum)));
+  if (int rc = h->rp_pin.ensure(sizeof(RpSum))) return rc;
   RpSum* const dsum = reinterpret_cast<RpSum*>(h->rp_sum.p);
-  const RpSum& s = *static_cast<const RpSum*>(h->rp_pin);
+  const RpSum& s = *static_cast<const RpSum*>(h->rp_pin.p);
   const bool mk = h->mesh_kernels();
   hipLaunchKernelGGL(k_repair_init, dim3(std::min<unsigned>(grid_for(W, 256), 1024)), dim3(256), 0,
                      h->stream, W, h->rp_gate[0].p, h->rp_gate[1].p, h->rp_dirty.p, h->rp_first.p,
@@ -222,7 +222,7 @@ int rp_passes(tcmp_handle* h, const double* wp, long long W, long long ni, int m
                        h->rp_gate[cur ^ 1].p, h->rp_first.p, h->rp_count.p, h->rp_dirty.p,
                        may_close, dsum);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(h->rp_pin, dsum, sizeof(RpSum), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(h->rp_pin.p, dsum, sizeof(RpSum), hipMemcpyDeviceToHost, h->stream));
     if (int rc_s = sync_stream(h)) return rc_s;
     r->passes_run = pass;
     r->segments_resampled += n_dirty;
@@ -303,18 +303,14 @@ int tcmp_repair_traj(tcmp_handle* h, const double* waypoints, int64_t n_wp, int6
   int max_passes, check_only;
   if (int rc = rp_cfg(cfg, &max_passes, &check_only)) return rc;
   if (!check_only && (!q || !qd || !qdd || !gates)) return fail(-1, "bad arguments");
-  if (int rc = h->rp_wp.ensure((size_t)n_wp * 7)) return rc;
-  HIPCHK(hipMemcpyAsync(h->rp_wp.p, waypoints, (size_t)n_wp * 7 * sizeof(double),
-                        hipMemcpyHostToDevice, h->stream));
+  if (int rc = upload(h, h->rp_wp, waypoints, (size_t)n_wp * 7)) return rc;
   int cur = 0;
   if (int rc = rp_run(h, h->rp_wp.p, n_wp, ni, max_passes, check_only, res, &cur)) return rc;
   if (res->status != TCMP_REPAIR_OK || check_only) return 0;
-  const size_t nb = (size_t)res->n_rows * 7 * sizeof(double);
-  HIPCHK(hipMemcpyAsync(q, h->rp_o[0].p, nb, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipMemcpyAsync(qd, h->rp_o[1].p, nb, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipMemcpyAsync(qdd, h->rp_o[2].p, nb, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipMemcpyAsync(gates, h->rp_gate[cur].p, (size_t)n_wp * sizeof(int), hipMemcpyDeviceToHost,
-                        h->stream));
+  double* const rows[3] = {q, qd, qdd};
+  for (int k = 0; k < 3; ++k)
+    if (int rc = download(h, rows[k], h->rp_o[k].p, (size_t)res->n_rows * 7)) return rc;
+  if (int rc = download(h, gates, h->rp_gate[cur].p, (size_t)n_wp)) return rc;
   return sync_stream(h);
 }
 
@@ -357,8 +353,8 @@ int tcmp_plan_repair(tcmp_handle* h, const tcmp_repair_cfg* cfg, tcmp_repair_res
                                 h->u0.p))
     return rc;
   res->ms += t.ms();
-  res->first_fail_after = h->pin->st.first_fail;
-  h->fin_status = h->pin->st.status;
+  res->first_fail_after = h->pin()->st.first_fail;
+  h->fin_status = h->pin()->st.status;
   h->fin_first_fail = res->first_fail_after;
   h->repaired = true;
   h->pl_gated = true;

@@ -401,17 +401,13 @@ int tcmp_retime_profile_traj(tcmp_handle* h, const double* q, const double* qd, 
   h->pf_host.resize(o_end * sizeof(double));
   double* const hs = reinterpret_cast<double*>(h->pf_host.data());
   if (int rc = stage_download_rows(h, hs + o_qd, hs + o_qdd, hs + o_psg, n)) return rc;
-  HIPCHK(hipMemcpyAsync(hs + o_x, h->pf_x.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost,
-                        h->stream));
-  HIPCHK(hipMemcpyAsync(hs + o_u, h->pf_u.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost,
-                        h->stream));
+  if (int rc = download(h, hs + o_x, h->pf_x.p, (size_t)n)) return rc;
+  if (int rc = download(h, hs + o_u, h->pf_u.p, (size_t)n)) return rc;
   HIPCHK(hipMemcpyAsync(hs + o_ff, h->pf_ff.p, (size_t)n_traj * sizeof(unsigned long long),
                         hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipMemcpyAsync(results, h->pf_res.p, (size_t)n_traj * sizeof(*results),
-                        hipMemcpyDeviceToHost, h->stream));
+  if (int rc = download(h, results, h->pf_res.p, (size_t)n_traj)) return rc;
   if (coef_out)
-    HIPCHK(hipMemcpyAsync(coef_out, h->pf_coef.p, (size_t)n * 18 * sizeof(double),
-                          hipMemcpyDeviceToHost, h->stream));
+    if (int rc = download(h, coef_out, h->pf_coef.p, (size_t)n * 18)) return rc;
   if (int rc_s = sync_stream(h)) return rc_s;
   const double dt = span.ms();
   if (ms) *ms = dt;

@@ -220,12 +220,9 @@ int rr_run(tcmp_handle* h, const double* q, const double* qd, const double* qdd,
   hipLaunchKernelGGL(k_rt_runs, dim3(std::min<unsigned>(grid_for(max_runs, 4), 4096)), dim3(256),
                      0, h->stream, drows, psg, h->rr_off.p, drun, h->rr_org.p);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(hoff, h->rr_off.p, (size_t)(max_runs + 2) * sizeof(long long),
-                        hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipMemcpyAsync(hpart, drun, (size_t)max_runs * sizeof(RtPart), hipMemcpyDeviceToHost,
-                        h->stream));
-  HIPCHK(hipMemcpyAsync(horg, h->rr_org.p, (size_t)max_runs * sizeof(double),
-                        hipMemcpyDeviceToHost, h->stream));
+  if (int rc = download(h, hoff, h->rr_off.p, (size_t)(max_runs + 2))) return rc;
+  if (int rc = download(h, hpart, drun, (size_t)max_runs)) return rc;
+  if (int rc = download(h, horg, h->rr_org.p, (size_t)max_runs)) return rc;
   t0.end();
   if (int rc_s = sync_stream(h)) return rc_s;
   r->ms = t0.ms();

@@ -286,12 +286,14 @@ __global__ __launch_bounds__(256) void k_sc_splice(const PlanParams* __restrict_
 // The passes over the list in bufs[*cur] (rows of 7): each pass reads one buffer and writes the
 // other; *cur names the buffer holding the result.  P: the distance weights, the extend
 // resolutions, the torque mode and the payload mass of the chord checks (and the execution time
-// of the tail); st: the state k_sc_splice's tail writes.  The chords' launch counts into the
-// engine's scratch state, so a plan's counters stay its own.  One host wait per pass.
+// of the tail); st: the state k_sc_splice's tail writes (null: the engine's scratch state).  The
+// chords' launch counts into that scratch state, so a plan's counters stay its own.  One host
+// wait per pass.
 int sc_run(tcmp_handle* h, const PlanParams& P, DevState* st, double* const bufs[2],
            const long long caps[2], int* cur, long long n, int a_max, int passes,
            tcmp_shortcut_result* r) {
-  if (!h->st_sc) HIPCHK(hipMalloc(&h->st_sc, sizeof(DevState)));
+  if (int rc = h->st_sc.ensure()) return rc;
+  if (!st) st = h->st_sc;
   if (int rc = h->sc_stats.ensure(sizeof(ScStats))) return rc;
   ScStats* dstats = reinterpret_cast<ScStats*>(h->sc_stats.p);
   HIPCHK(hipMemcpyAsync(h->dPx, &P, sizeof(P), hipMemcpyHostToDevice, h->stream));
@@ -320,11 +322,7 @@ int sc_run(tcmp_handle* h, const PlanParams& P, DevState* st, double* const bufs
     if (g.C > 0) {
       const EdgeJob J{h->sc_from.p, nullptr, h->sc_to.p, g.C, h->sc_nsafe.p, h->sc_nsteps.p,
                       h->sc_last.p, nullptr, nullptr, h->sc_rec.p};
-      DevState* const plan_st = h->st;
-      h->st = h->st_sc;
-      rc = launch_edges(h, J, h->dPx);
-      h->st = plan_st;
-      if (rc) return rc;
+      if ((rc = launch_edges(h, h->st_sc, J, h->dPx))) return rc;
     }
     hipLaunchKernelGGL(k_sc_dp, dim3(1), dim3(1024), 0, h->stream, h->dPx, in, g, h->sc_kl.p,
                        h->sc_nsafe.p, h->sc_nsteps.p, h->sc_last.p, h->sc_len.p, h->sc_orig.p,
@@ -408,17 +406,14 @@ int tcmp_shortcut_path(tcmp_handle* h, const double* waypoints, int64_t n_wp,
   int rc = h->sc_wp[0].ensure((size_t)cap * 7);
   rc = rc ? rc : h->sc_wp[1].ensure((size_t)cap * 7);
   if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(h->sc_wp[0].p, waypoints, (size_t)n_wp * 7 * sizeof(double),
-                        hipMemcpyHostToDevice, h->stream));
+  if ((rc = upload(h, h->sc_wp[0], waypoints, (size_t)n_wp * 7))) return rc;
   double* const bufs[2] = {h->sc_wp[0].p, h->sc_wp[1].p};
   const long long caps[2] = {cap, cap};
   int cur = 0;
   // (the tail's plan fields go to the scratch state: no plan is touched)
-  if (!h->st_sc) HIPCHK(hipMalloc(&h->st_sc, sizeof(DevState)));
-  if ((rc = sc_run(h, P, h->st_sc, bufs, caps, &cur, n_wp, a_max, passes, res))) return rc;
+  if ((rc = sc_run(h, P, nullptr, bufs, caps, &cur, n_wp, a_max, passes, res))) return rc;
   if (res->n_after > cap_out) return fail(-4, "output capacity too small");
-  HIPCHK(hipMemcpyAsync(out, bufs[cur], (size_t)res->n_after * 7 * sizeof(double),
-                        hipMemcpyDeviceToHost, h->stream));
+  if ((rc = download(h, out, bufs[cur], (size_t)res->n_after * 7))) return rc;
   return sync_stream(h);
 }
 
@@ -435,7 +430,7 @@ int tcmp_plan_shortcut(tcmp_handle* h, const tcmp_shortcut_cfg* cfg, tcmp_shortc
                      Tree{h->cfg.p, h->parent.p, h->tgt.p, h->meta.p}, h->chain.p, h->wp.p,
                      (long long)(h->wp.n / 7));
   HIPCHK(hipGetLastError());
-  DevState& s = h->pin->st;
+  DevState& s = h->pin()->st;
   HIPCHK(hipMemcpyAsync(&s, h->st, sizeof(DevState), hipMemcpyDeviceToHost, h->stream));
   if (int rc_s = sync_stream(h)) return rc_s;
   if (s.goal_node < 0) {

@@ -131,29 +131,19 @@ bool stage_applicable(const tcmp_handle* h) {
 // into h->rt_in[0..3] ...
 int stage_upload_rows(tcmp_handle* h, const double* q, const double* qd, const double* qdd,
                       const double* psg, long long n) {
-  int rc = 0;
-  for (int k = 0; k < 3; ++k) rc = rc ? rc : h->rt_in[k].ensure((size_t)n * 7);
-  rc = rc ? rc : h->rt_in[3].ensure((size_t)n);
-  if (rc) return rc;
+  int rc = psg ? 0 : h->rt_in[3].ensure((size_t)n);
   const double* src[3] = {q, qd, qdd};
-  for (int k = 0; k < 3; ++k)
-    HIPCHK(hipMemcpyAsync(h->rt_in[k].p, src[k], (size_t)n * 7 * sizeof(double),
-                          hipMemcpyHostToDevice, h->stream));
-  if (psg)
-    HIPCHK(hipMemcpyAsync(h->rt_in[3].p, psg, (size_t)n * sizeof(double), hipMemcpyHostToDevice,
-                          h->stream));
-  return 0;
+  for (int k = 0; k < 3; ++k) rc = rc ? rc : upload(h, h->rt_in[k], src[k], (size_t)n * 7);
+  if (psg) rc = rc ? rc : upload(h, h->rt_in[3], psg, (size_t)n);
+  return rc;
 }
 
 // ... and out: h->rt_o[0..2] into the caller's (psg: null to leave it out).  Enqueued only.
 int stage_download_rows(tcmp_handle* h, double* qd, double* qdd, double* psg, long long n) {
-  HIPCHK(hipMemcpyAsync(qd, h->rt_o[0].p, (size_t)n * 7 * sizeof(double), hipMemcpyDeviceToHost,
-                        h->stream));
-  HIPCHK(hipMemcpyAsync(qdd, h->rt_o[1].p, (size_t)n * 7 * sizeof(double), hipMemcpyDeviceToHost,
-                        h->stream));
+  if (int rc = download(h, qd, h->rt_o[0].p, (size_t)n * 7)) return rc;
+  if (int rc = download(h, qdd, h->rt_o[1].p, (size_t)n * 7)) return rc;
   if (psg)
-    HIPCHK(hipMemcpyAsync(psg, h->rt_o[2].p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost,
-                          h->stream));
+    if (int rc = download(h, psg, h->rt_o[2].p, (size_t)n)) return rc;
   return 0;
 }
 
@@ -180,8 +170,8 @@ int plan_commit_rows(tcmp_handle* h, StageSpan& t, long long K, const double* q,
   if (first_fail)
     HIPCHK(hipMemcpyAsync(&ff, first_fail, sizeof(ff), hipMemcpyDeviceToHost, h->stream));
   if (int rc_s = sync_stream(h)) return rc_s;
-  h->pin->st.status = ff == kNoRow ? TCMP_PLAN_OK : TCMP_PLAN_VALIDATION_FAILED;
-  h->pin->st.first_fail = ff == kNoRow ? -1 : (long long)ff;
+  h->pin()->st.status = ff == kNoRow ? TCMP_PLAN_OK : TCMP_PLAN_VALIDATION_FAILED;
+  h->pin()->st.first_fail = ff == kNoRow ? -1 : (long long)ff;
   return 0;
 }
 
