@@ -248,6 +248,68 @@ int tcmp_shortcut_path(tcmp_handle* h, const double* waypoints, int64_t n_wp,
                        double payload_mass, const tcmp_shortcut_cfg* cfg, double* out,
                        int64_t cap_out, tcmp_shortcut_result* res);
 
+/* Best-parent goal connection over the whole tree (no reference counterpart: the reference tries
+ * the goal from the node nearest to it only, and never again once goal_n exists,
+ * rrt_star.py:160-161, so goal_n.cost never improves).  Opt-in, between the rounds and the
+ * shortcut or finish; it changes nothing unless called.
+ *
+ * Inputs: nodes i = 0 .. T-1 with configuration c_i and cost g_i >= 0, the target G, the weights
+ * w and a bound B -- +inf without a goal node, else the current goal node's cost (the plan form
+ * reads it from the tree row).
+ *   key       key_i = g_i + distance(c_i, G, w), the distance fn summed in joint order
+ *             (s += w_k * (d * d), sqrt, no contraction), then the one add
+ *   eligible  key_i < B, strictly; a NaN key fails.  The goal node and everything below it are
+ *             therefore never eligible; there is no other exclusion
+ *   selected  M = min(n_eligible, K * passes); the M eligible nodes smallest by (key, i), in that
+ *             order (ties to the lowest index); K = max_candidates
+ *   pass p    tests ranks [p K, min(M, (p + 1) K)): each candidate's edge c_i -> G goes through
+ *             tcmp_check_edges' check (safe_path_force_aware(extend(c_i, G)), the static torque
+ *             test) with the call's resolutions, torque mode, payload mass and scene.  A
+ *             candidate is valid iff n_safe > 0 and distance(last, G, w) < goal_tolerance (the
+ *             test of a round's goal lane); its new cost is c = g_i + distance(c_i, last, w).
+ *             The pass's winner is the valid candidate with c < B smallest by (c, rank).  The
+ *             first pass with a winner ends the stage: later ranks are not tested
+ *   outcome   OK with the winner; NONE when no pass had one (n_eligible == 0 included, then
+ *             passes_run = 0); the plan form only: TREE_FULL when a winner exists but
+ *             n_nodes == max_nodes.  NONE and TREE_FULL leave everything as it was, bit for bit
+ * The ranking is by the straight-line key, so candidates behind one obstacle cluster together;
+ * `passes` is the answer to that.  Deterministic: equal calls give equal bytes. */
+#define TCMP_CONNECT_OK 0
+#define TCMP_CONNECT_NONE 1
+#define TCMP_CONNECT_TREE_FULL 2
+
+typedef struct {
+  int32_t max_candidates;    /* K: 1..65536, 0 = 1024 */
+  int32_t passes;            /* 1..8, 0 = 1 */
+} tcmp_connect_cfg;
+
+typedef struct {
+  int32_t status, passes_run;
+  int64_t n_nodes, n_eligible, n_selected, n_tested, n_valid; /* tested, valid: the passes run */
+  uint64_t edge_steps;       /* extend steps of the tested edges */
+  int64_t goal_node_before, goal_node_after;  /* -1: none (the stand-alone form: both -1) */
+  int64_t parent, rank;      /* the winner (TREE_FULL too), -1: none */
+  double cost_before;        /* the goal node's cost; 0 without a goal (stand-alone: 0) */
+  double cost_after;         /* OK: the new cost; else cost_before */
+  double key_min;            /* smallest eligible key: no connection can beat it;
+                                0 when n_eligible == 0 */
+  double ms;                 /* device time of the stage (0 with timing off) */
+} tcmp_connect_result;
+
+/* the stage on n given nodes (nodes n x 7, cost n, 1 <= n <= INT_MAX, costs not negative) in
+ * the scene set on the handle; bound = INFINITY: none.  resolutions (7, NULL = 0.1), weights (7,
+ * NULL = 10).  ids_out, keys_out (cap_out each): the M selected, in rank order; nsafe_out,
+ * nsteps_out (cap_out each): the verdicts of the tested ranks, -1 for ranks a stopped stage never
+ * tested; cap_out < M with one of the four given: status -4 with res->n_selected set.  node_out
+ * (8): on OK the winner's record, `last` (7 values) then c.  Any output pointer may be NULL.
+ * Leaves an open plan alone. */
+int tcmp_connect_nodes(tcmp_handle* h, const double* nodes, const double* cost, int64_t n,
+                       const double* goal, double bound, const double* resolutions,
+                       const double* weights, double goal_tolerance, int32_t torque_mode,
+                       double payload_mass, const tcmp_connect_cfg* cfg, int32_t* ids_out,
+                       double* keys_out, int32_t* nsafe_out, int32_t* nsteps_out, int64_t cap_out,
+                       double* node_out, tcmp_connect_result* res);
+
 /* argmin over tree nodes of the weighted distance (rrt_star.py:9-14,171), first index wins
  * ties.  tree: T x 7, samples: n x 7, weights: 7 positive (NULL = 10 = 1/radius).  Runs the
  * planner's own nearest path: the radix-tree cell index of the tree and the pruned exact
@@ -404,6 +466,21 @@ int tcmp_plan_retrace(tcmp_handle* h, tcmp_plan_result* result);
  * tree's, and the plan's counters do not include the chords' (those are in `res`).  Without a
  * goal node: res->status = TCMP_PLAN_NO_GOAL and nothing changes. */
 int tcmp_plan_shortcut(tcmp_handle* h, const tcmp_shortcut_cfg* cfg, tcmp_shortcut_result* res);
+
+/* tcmp_connect_nodes' stage on the open plan's tree, with the plan's own goal, weights,
+ * resolutions, goal tolerance, torque mode and payload mass.  On OK one node is appended at index
+ * n_nodes with exactly the record a round's insertion writes (configuration = last, cost = c,
+ * parent = i, extend target = G, its step counts), so the retrace regenerates the edge; n_nodes
+ * grows by one and the new node is the goal node -- the old goal node stays as an ordinary node.
+ * A stored shortcut list is dropped and the finished rows are invalidated, as by
+ * tcmp_plan_shortcut (retime and repair are NOT_APPLICABLE until the next finish).  The plan's
+ * counters are untouched (the edges' are in `res`).  No rewire pass runs around the new node.
+ * Afterwards tcmp_plan_goal, tcmp_plan_digest, tcmp_plan_tree, the retrace, shortcut, finish and
+ * further rounds see the new node; a plan meant to grow after a connection needs max_nodes one
+ * above 1 + its samples.  A fleet member is connected on its own engine after
+ * tcmp_plan_run_fused; the ranks of a shared tree must each call it (determinism keeps them
+ * equal). */
+int tcmp_plan_connect(tcmp_handle* h, const tcmp_connect_cfg* cfg, tcmp_connect_result* res);
 
 /* Torque-feasible retiming (no reference counterpart: the reference returns nothing when one
  * row of the trajectory fails the final torque test, rrt_star.py:208-210).  Playing the same rows

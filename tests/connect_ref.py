@@ -1,0 +1,163 @@
+"""Restatement of the best-parent goal connection (include/tcmp.h tcmp_connect_nodes,
+tcmp_plan_connect), the reference of tests/test_connect_host.py and tests/test_gpu_connect.py.
+Nothing here imports the package: the edge check is injected (oracle_check: the CPU oracle's
+check_edge, resolutions 0.1), distances are the distance fn in scalar fp64 in joint order.
+
+  key       key_i = g_i + dist(c_i, G)
+  eligible  key_i < B, strictly (a NaN key fails); B = +inf without a goal node, else its cost
+  selected  M = min(n_eligible, K * passes), the M eligible smallest by (key, i)
+  pass p    ranks [p K, min(M, (p + 1) K)): check(c_i, G) -> (n_safe, n_steps, last); valid iff
+            n_safe > 0 and dist(last, G) < tol; c = g_i + dist(c_i, last); the winner is the valid
+            one with c < B smallest by (c, rank); the first pass with a winner ends the stage
+  outcome   OK (0), NONE (1), or -- with max_nodes given and n == max_nodes -- TREE_FULL (2)
+"""
+import math
+
+import numpy as np
+
+OK, NONE, TREE_FULL = 0, 1, 2
+W10 = (10.0,) * 7
+
+
+def distance(a, b, w=W10):
+    """sqrt(sum_k w_k * (d_k * d_k)), k = 0..6 in order, one fp64 operation after the other."""
+    s = 0.0
+    for k in range(7):
+        d = float(b[k]) - float(a[k])
+        s += float(w[k]) * (d * d)
+    return math.sqrt(s)
+
+
+def keys(cfg, cost, G, w=W10):
+    """key_i for all rows at once: the same operations in the same order, elementwise."""
+    cfg = np.asarray(cfg, dtype=np.float64).reshape(-1, 7)
+    s = np.zeros(len(cfg))
+    for k in range(7):
+        d = np.float64(G[k]) - cfg[:, k]
+        s = s + np.float64(w[k]) * (d * d)
+    return np.asarray(cost, dtype=np.float64) + np.sqrt(s)
+
+
+def select(key, bound, K, passes):
+    """-> (ids of the M selected in rank order, n_eligible)."""
+    with np.errstate(invalid="ignore"):
+        el = np.nonzero(key < bound)[0]
+    order = el[np.lexsort((el, key[el]))]
+    return order[:min(len(el), K * passes)], len(el)
+
+
+def connect(cfg, cost, G, check, bound=math.inf, w=W10, tol=1e-2, K=1024, passes=1,
+            goal_node=-1, max_nodes=None):
+    """check(a, b) -> (n_safe, n_steps, last).  goal_node >= 0: the plan form's bound, that
+    node's cost.  -> dict: the result record's fields (but ms), ids / keys / nsafe / nsteps of the
+    M selected (-1: not tested), and on OK or TREE_FULL `node` (last (7), c) and `meta`
+    (n_steps, n_safe) of the winner."""
+    cfg = np.asarray(cfg, dtype=np.float64).reshape(-1, 7)
+    cost = np.asarray(cost, dtype=np.float64).reshape(-1)
+    T = len(cfg)
+    if goal_node >= 0:
+        bound = float(cost[goal_node])
+    key = keys(cfg, cost, G, w)
+    ids, n_el = select(key, bound, K, passes)
+    M = len(ids)
+    nsafe = np.full(M, -1, dtype=np.int32)
+    nsteps = np.full(M, -1, dtype=np.int32)
+    r = dict(status=NONE, passes_run=0, n_nodes=T, n_eligible=n_el, n_selected=M, n_tested=0,
+             n_valid=0, edge_steps=0, goal_node_before=goal_node, goal_node_after=goal_node,
+             parent=-1, rank=-1, cost_before=float(cost[goal_node]) if goal_node >= 0 else 0.0,
+             key_min=float(key[ids[0]]) if M else 0.0)
+    r["cost_after"] = r["cost_before"]
+    node = meta = None
+    for p in range(passes):
+        if p * K >= M:
+            break
+        best = None
+        for rank in range(p * K, min(M, (p + 1) * K)):
+            i = int(ids[rank])
+            ns, nt, last = check(cfg[i], G)
+            nsafe[rank], nsteps[rank] = ns, nt
+            r["n_tested"] += 1
+            r["edge_steps"] += nt if ns == nt else ns + 1
+            if ns > 0 and distance(last, G, w) < tol:
+                r["n_valid"] += 1
+                c = float(cost[i]) + distance(cfg[i], last, w)
+                if c < bound and (best is None or c < best[0]):
+                    best = (c, rank, i, np.array(last, dtype=np.float64), nt, ns)
+        r["passes_run"] = p + 1
+        if best is not None:
+            c, rank, i, last, nt, ns = best
+            r["parent"], r["rank"] = i, rank
+            node, meta = np.concatenate([last, [c]]), (nt, ns)
+            if max_nodes is not None and T == max_nodes:
+                r["status"] = TREE_FULL
+            else:
+                r["status"] = OK
+                r["cost_after"] = c
+                if max_nodes is not None:
+                    r["goal_node_after"] = T
+            break
+    return dict(result=r, ids=ids.astype(np.int32), keys=key[ids], nsafe=nsafe, nsteps=nsteps,
+                node=node, meta=meta)
+
+
+def oracle_check(O, obs, mode, mass):
+    """check(a, b) through the CPU oracle's check_edge (Gauss-map exact test, cull=2)."""
+    def check(a, b):
+        return O.check_edge(a, b, obs, mode, mass, cull=2)
+    return check
+
+
+# ---- the fixtures the host and GPU tests share -----------------------------------------------
+# (only the scenes below come from the package; the restatement above imports nothing of it)
+LO = np.array([-2.8973, -1.7628, -2.8973, -3.0718, -2.8973, -0.0175, -2.8973])
+HI = np.array([2.8973, 1.7628, 2.8973, -0.0698, 2.8973, 3.7525, 2.8973])
+START = np.array([0, -np.pi / 4, 0.0, -6 * np.pi / 8, 0, np.pi / 2, np.pi / 4])
+MODE, MASS, SAMPLES, BATCH, EXEC = 2, 5.0, 3072, 256, 1.0
+# name: (boxes, scene / goal seed, K, passes) -- batched plans at B = 256 over 3,072 samples
+FIXTURES = {
+    "improves": (16, 2, 64, 1),    # a goal node exists; a cheaper parent is among the first 64
+    "rescues": (32, 2, 64, 1),     # no goal node; one of the first 64 reaches the goal
+    "none": (16, 11, 64, 1),       # no goal node, and none of the first 64 reaches it
+    "passes3": (16, 11, 64, 3),    # ... the third 64 do
+    "no_eligible": (16, 1, 64, 1),  # the goal hangs off the root: nothing can beat it
+}
+
+
+def query(O, n_obs, seed):
+    """tests/test_gpu_shortcut.py's plan_query recipe: the first draw of (goal, 16 or 32 random
+    boxes) whose start and goal are collision-free and within the torque limits; plan seed
+    100 + seed."""
+    from torque_constrained_motion_planning_amd.scene import obstacle_array, random_box_scene
+    rng = np.random.default_rng(seed)
+    while True:
+        goal = LO + (HI - LO) * rng.random(7)
+        obs = obstacle_array(random_box_scene(rng, n_obs)) if n_obs else np.zeros((0, 15))
+        if O.collision(START, obs) or O.collision(goal, obs):
+            continue
+        if O.torque_ok(goal, MODE, MASS) and O.torque_ok(START, MODE, MASS):
+            return dict(obs=obs, pack=None, self_coll=False, mode=MODE, mass=MASS, goal=goal,
+                        seed=100 + seed)
+
+
+def purpose(name, r):
+    """Does the fixture still serve its purpose?  -> None, or what is wrong."""
+    want = {
+        "improves": r["goal_node_before"] >= 0 and r["status"] == OK
+        and r["cost_after"] < r["cost_before"] and 0 < r["n_valid"] < r["n_tested"],
+        "rescues": r["goal_node_before"] < 0 and r["status"] == OK and r["rank"] > 0,
+        "none": r["goal_node_before"] < 0 and r["status"] == NONE and r["n_tested"] == 64
+        and r["n_valid"] == 0,
+        "passes3": r["goal_node_before"] < 0 and r["status"] == OK and r["passes_run"] == 3,
+        "no_eligible": r["goal_node_before"] >= 0 and r["status"] == NONE
+        and r["n_eligible"] == 0 and r["passes_run"] == 0,
+    }[name]
+    return None if want else (name, r, "the fixture proves nothing")
+
+
+def ancestors(parent, i):
+    """root .. i"""
+    out = []
+    while i >= 0:
+        out.append(int(i))
+        i = int(parent[i])
+    return out[::-1]

@@ -37,6 +37,7 @@ EXPORTS = [
     "tcmp_dist_barrier", "tcmp_dist_allreduce", "tcmp_dist_allgather_i64", "tcmp_gather_paths",
     "tcmp_gather_layout", "tcmp_gather_pack", "tcmp_gather_unpack", "tcmp_dist_rccl_ranks",
     "tcmp_shortcut_path", "tcmp_plan_shortcut",
+    "tcmp_connect_nodes", "tcmp_plan_connect",
     "tcmp_retime_traj", "tcmp_plan_retime",
     "tcmp_repair_traj", "tcmp_plan_repair",
     "tcmp_minjerk_runs", "tcmp_retime_runs_traj", "tcmp_plan_retime_runs",
@@ -116,6 +117,32 @@ class ShortcutResult(ctypes.Structure):
         ("chords_tested", ctypes.c_uint64), ("chords_valid", ctypes.c_uint64),
         ("chords_used", ctypes.c_uint64), ("chord_steps", ctypes.c_uint64),
         ("ms", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+# tcmp_connect_result.status (include/tcmp.h)
+CONNECT_OK, CONNECT_NONE, CONNECT_TREE_FULL = range(3)
+
+
+class ConnectCfg(ctypes.Structure):
+    """tcmp_connect_cfg"""
+    _fields_ = [("max_candidates", ctypes.c_int32), ("passes", ctypes.c_int32)]
+
+
+class ConnectResult(ctypes.Structure):
+    """tcmp_connect_result"""
+    _fields_ = [
+        ("status", ctypes.c_int32), ("passes_run", ctypes.c_int32),
+        ("n_nodes", ctypes.c_int64), ("n_eligible", ctypes.c_int64),
+        ("n_selected", ctypes.c_int64), ("n_tested", ctypes.c_int64),
+        ("n_valid", ctypes.c_int64), ("edge_steps", ctypes.c_uint64),
+        ("goal_node_before", ctypes.c_int64), ("goal_node_after", ctypes.c_int64),
+        ("parent", ctypes.c_int64), ("rank", ctypes.c_int64),
+        ("cost_before", ctypes.c_double), ("cost_after", ctypes.c_double),
+        ("key_min", ctypes.c_double), ("ms", ctypes.c_double),
     ]
 
     def as_dict(self):
@@ -317,6 +344,14 @@ def load_library(path=LIB_PATH):
                                              ctypes.c_int64, ctypes.POINTER(ShortcutResult)]
             L.tcmp_plan_shortcut.argtypes = [vp, ctypes.POINTER(ShortcutCfg),
                                              ctypes.POINTER(ShortcutResult)]
+        if hasattr(L, "tcmp_connect_nodes"):  # absent from A/B builds of older sources
+            L.tcmp_connect_nodes.argtypes = [vp, _dp, _dp, ctypes.c_int64, _dp, ctypes.c_double,
+                                             _dp, _dp, ctypes.c_double, ctypes.c_int32,
+                                             ctypes.c_double, ctypes.POINTER(ConnectCfg), _i32p,
+                                             _dp, _i32p, _i32p, ctypes.c_int64, _dp,
+                                             ctypes.POINTER(ConnectResult)]
+            L.tcmp_plan_connect.argtypes = [vp, ctypes.POINTER(ConnectCfg),
+                                            ctypes.POINTER(ConnectResult)]
         if hasattr(L, "tcmp_retime_traj"):  # absent from A/B builds of older sources
             L.tcmp_retime_traj.argtypes = [vp, _dp, _dp, _dp, _dp, ctypes.c_int64, ctypes.c_int32,
                                            ctypes.c_double, ctypes.POINTER(RetimeCfg), _dp, _dp,
@@ -679,6 +714,47 @@ class Engine:
         cfg = ShortcutCfg(int(max_anchors), int(passes))
         r = ShortcutResult()
         self._check(self.L.tcmp_plan_shortcut(self.h, ctypes.byref(cfg), ctypes.byref(r)))
+        return r
+
+    def connect_nodes(self, nodes, cost, goal, torque_mode, payload_mass, bound=np.inf,
+                      resolutions=None, weights=None, goal_tolerance=1e-2, max_candidates=1024,
+                      passes=1):
+        """tcmp_connect_nodes: best-parent goal connection over given nodes (n, 7) with costs (n,)
+        in the scene set on this engine -> dict(ids, keys: the selected nodes in rank order;
+        nsafe, nsteps: their verdicts, -1 where not tested; node: the winner's (last, c) as (8,)
+        or None; result: the ConnectResult)."""
+        self._need("tcmp_connect_nodes")
+        q = _rows(nodes, "nodes")
+        g = np.ascontiguousarray(cost, dtype=np.float64).reshape(-1)
+        if len(g) != len(q):
+            raise ValueError("cost must hold one value per node")
+        G = np.ascontiguousarray(goal, dtype=np.float64).reshape(7)
+        res = None if resolutions is None else np.ascontiguousarray(resolutions, dtype=np.float64)
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
+        cfg = ConnectCfg(int(max_candidates), int(passes))
+        r = ConnectResult()
+        cap = min(len(q), max(int(max_candidates), 1) * max(int(passes), 1))
+        ids = np.zeros(cap, dtype=np.int32)
+        keys = np.zeros(cap)
+        ns = np.zeros(cap, dtype=np.int32)
+        nt = np.zeros(cap, dtype=np.int32)
+        node = np.zeros(8)
+        self._check(self.L.tcmp_connect_nodes(
+            self.h, _d(q), _d(g), len(q), _d(G), float(bound), _d(res), _d(w),
+            float(goal_tolerance), int(torque_mode), float(payload_mass), ctypes.byref(cfg),
+            ids.ctypes.data_as(_i32p), _d(keys), ns.ctypes.data_as(_i32p),
+            nt.ctypes.data_as(_i32p), cap, _d(node), ctypes.byref(r)))
+        m = int(r.n_selected)
+        return dict(ids=ids[:m].copy(), keys=keys[:m].copy(), nsafe=ns[:m].copy(),
+                    nsteps=nt[:m].copy(), node=node if r.status == CONNECT_OK else None, result=r)
+
+    def plan_connect(self, max_candidates=1024, passes=1):
+        """tcmp_plan_connect: try the goal from the best nodes of the open plan's whole tree; on
+        CONNECT_OK the tree has one more node, the new goal node."""
+        self._need("tcmp_plan_connect")
+        cfg = ConnectCfg(int(max_candidates), int(passes))
+        r = ConnectResult()
+        self._check(self.L.tcmp_plan_connect(self.h, ctypes.byref(cfg), ctypes.byref(r)))
         return r
 
     def retime(self, q, qd, qdd, mode, mass, psg=None, min_scale=1.0, max_scale=0.0):

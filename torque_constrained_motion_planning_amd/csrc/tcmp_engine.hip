@@ -1660,6 +1660,17 @@ struct tcmp_handle {
   DBuf<int> gs_cnt, gs_list, gs_lid, gs_oid;
   DBuf<unsigned long long> gs_key, gs_lkey, gs_ctr;
   double gs_refw_h[14] = {};  // (ref, weights) on the host until their upload has run
+  // goal connection (tcmp_connect.h): the stand-alone call's rows, one key per node, the
+  // selection's state and the pass's outcome, the selected (key, index) rows and their sort's
+  // double and scratch, the ranks' verdicts, the pass's targets, last points and work records;
+  // extra_nodes: nodes of the open plan that no round added (tcmp_plan_connect), which the
+  // rounds' host-side bound on the tree size (1 + samples issued) has to include
+  DBuf<double> cn_rows, cn_to, cn_last, cn_rec;
+  DBuf<unsigned long long> cn_key, cn_skey[2];
+  DBuf<unsigned> cn_sidx[2];
+  DBuf<int> cn_nsafe, cn_nsteps;
+  DBuf<unsigned char> cn_state, cn_tmp;
+  long long extra_nodes = 0;
   int edge_split = 4; // most lanes per edge in small rounds (environment TCMP_EDGE_SPLIT=1/2/4)
   int edge_wps = 2;    // k_edges' persistent grid, blocks per CU (environment TCMP_EDGE_WPS=1/2)
 
@@ -3351,6 +3362,7 @@ int plan_begin_launch(tcmp_handle* h, const tcmp_plan_cfg* cfg, tcmp_plan_result
   if (rc) return rc;
   h->max_batch = cfg->max_batch;
   h->samples_issued = 0;
+  h->extra_nodes = 0;
   h->collect_events();
   for (double& m : h->ms) m = 0;
   h->launches_nearest = 0;
@@ -3471,6 +3483,7 @@ static unsigned long long round_graph_key(const tcmp_handle* h, long long n_samp
   };
   auto mixp = [&](const void* p) { mix((unsigned long long)(uintptr_t)p); };
   mix((unsigned long long)h->samples_issued);
+  mix((unsigned long long)h->extra_nodes);
   mix((unsigned long long)n_samples);
   mix((unsigned long long)batch);
   mix((unsigned long long)h->P.uniform_w);
@@ -3561,10 +3574,11 @@ static int round_search(tcmp_handle* h, bool device_samples, int32_t nb, long lo
   const int nblk = (int)grid_for(nb, 256);
   if (int rc = h->bcount.ensure(nblk)) return rc;
   if (int rc = h->boff.ensure(nblk)) return rc;
-  // the snapshot holds at most 1 + (samples issued before this round) nodes
+  // the snapshot holds at most 1 + (samples issued before this round) nodes, and those a goal
+  // connection appended
   hipEvent_t e1 = nullptr;  // the scan's end event also ends the family and begins the edges
   {
-    const long long T_bound = 1 + h->samples_issued - B;
+    const long long T_bound = 1 + h->samples_issued - B + h->extra_nodes;
     if (int rc = launch_nearest(h, P, h->dP, h->st, h->cfg.p, T_bound, h->cand.p, nb, h->nn.p,
                                 h->second.p, h->nnscore.p, &e1, gf, h->bcount.p))
       return rc;
@@ -3670,7 +3684,8 @@ static int sr_check(tcmp_handle* h, long long n_samples, int batch, int world) {
   if (batch < world) return fail(-1, "a shared-tree round needs at least one lane per engine");
   if ((batch + world - 1) / world > h->max_batch)
     return fail(-1, "batch / engines exceeds the plan's max_batch");
-  if (h->samples_issued + n_samples + 1 > h->P.max_nodes) return fail(-3, "tree capacity exceeded");
+  if (h->samples_issued + n_samples + 1 + h->extra_nodes > h->P.max_nodes)
+    return fail(-3, "tree capacity exceeded");
   return h->xch.ensure(3 + (size_t)world);
 }
 int tcmp_plan_round(tcmp_handle* h, const double* samples, const uint8_t* is_goal, int32_t nb,
@@ -3678,7 +3693,8 @@ int tcmp_plan_round(tcmp_handle* h, const double* samples, const uint8_t* is_goa
   TCMP_ENTER(h);
   if (!h->plan_open) return fail(-1, "no open plan (tcmp_plan_begin first)");
   if (nb < 1 || nb > h->max_batch) return fail(-1, "batch size out of range");
-  if (h->samples_issued + nb + 1 > h->P.max_nodes) return fail(-3, "tree capacity exceeded");
+  if (h->samples_issued + nb + 1 + h->extra_nodes > h->P.max_nodes)
+    return fail(-3, "tree capacity exceeded");
   if (int rc = plan_round_impl(h, samples, is_goal, nb)) return rc;
   if (goal_found) {
     long long g = -1;
@@ -3916,7 +3932,8 @@ int tcmp_plan_run(tcmp_handle* h, int64_t n_samples, int32_t batch) {
   TCMP_ENTER(h);
   if (!h->plan_open) return fail(-1, "no open plan (tcmp_plan_begin first)");
   if (batch < 1 || batch > h->max_batch) return fail(-1, "batch size out of range");
-  if (h->samples_issued + n_samples + 1 > h->P.max_nodes) return fail(-3, "tree capacity exceeded");
+  if (h->samples_issued + n_samples + 1 + h->extra_nodes > h->P.max_nodes)
+    return fail(-3, "tree capacity exceeded");
   auto run_rounds = [&]() -> int {
     long long left = n_samples;
     while (left > 0) {
@@ -4322,6 +4339,7 @@ int tcmp_plan_debug_round(tcmp_handle* h, int64_t cap, double* cand, int32_t* nn
 #include "tcmp_fleet.h"
 #include "tcmp_stage.h"
 #include "tcmp_shortcut.h"
+#include "tcmp_connect.h"
 #include "tcmp_retime.h"
 #include "tcmp_repair.h"
 #include "tcmp_retime_runs.h"

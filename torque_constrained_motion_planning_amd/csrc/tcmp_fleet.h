@@ -595,6 +595,7 @@ struct Fleet {
   tcmp_handle* h;          // the lead engine: stream, index buffers, descriptors
   int K;
   int bp, pb;              // lane stride per plan, plan-id key bits
+  long long extra;         // nodes no round added, the most over the plans (tcmp_plan_connect)
   int lds_obs;             // obstacles over all plans (the fused k_edges' LDS)
   int max_obs;             // the largest plan scene (k_fl_rewire_apply's LDS)
   bool mesh;               // mesh scenes: every plan's scene is the lead's
@@ -628,7 +629,8 @@ int fleet_round(const Fleet& F, int nb, long long base) {
   h->mark_begin(F_NEAREST, &e0);
   hipLaunchKernelGGL(k_fl_sample, pg, b256, 0, h->stream, F.fp, base, nb, bpb);
   HIPCHK(hipGetLastError());
-  const long long Tb = 1 + base;  // the snapshot bound: 1 + samples issued before the round
+  // the snapshot bound: 1 + samples issued before the round (+ connected goal nodes)
+  const long long Tb = 1 + base + F.extra;
   if (Tb == 1) {
     hipLaunchKernelGGL(k_fl_root, pg, b256, 0, h->stream, F.fp, nb, bpb);
     HIPCHK(hipGetLastError());
@@ -804,6 +806,7 @@ int tcmp_plan_run_fused(tcmp_handle* const* hs, int32_t n, int64_t n_samples, in
   tcmp_handle* h = hs[0];
   TCMP_ENTER(h);
   if (batch < 1) return fail(-1, "batch size out of range");
+  long long F_extra = 0;  // the most nodes a goal connection appended to one of the plans
   for (int q = 0; q < n; ++q) {
     tcmp_handle* e = hs[q];
     if (!e) return fail(-1, "null handle");
@@ -814,7 +817,9 @@ int tcmp_plan_run_fused(tcmp_handle* const* hs, int32_t n, int64_t n_samples, in
     if (batch > e->max_batch) return fail(-1, "batch size out of range");
     if (e->samples_issued != h->samples_issued)
       return fail(-1, "the fleet's plans are not at the same round");
-    if (e->samples_issued + n_samples + 1 > e->P.max_nodes) return fail(-3, "tree capacity exceeded");
+    if (e->samples_issued + n_samples + 1 + e->extra_nodes > e->P.max_nodes)
+      return fail(-3, "tree capacity exceeded");
+    F_extra = std::max(F_extra, e->extra_nodes);
     // mesh scenes (and self-collision pairs): one scene for the whole fleet, the lead's --
     // replica trees of one query (C5)
     if ((e->mesh_kernels() || h->mesh_kernels()) && !same_scene(e, h))
@@ -826,6 +831,7 @@ int tcmp_plan_run_fused(tcmp_handle* const* hs, int32_t n, int64_t n_samples, in
   if (n_samples <= 0) return 0;
   Fleet F{};
   F.h = h;
+  F.extra = F_extra;
   F.K = n;
   F.bp = (batch + 255) / 256 * 256;
   F.pb = 1;
@@ -845,7 +851,7 @@ int tcmp_plan_run_fused(tcmp_handle* const* hs, int32_t n, int64_t n_samples, in
     return fail(-1, "too many obstacles over the fleet's scenes for the fused edge kernel");
   // the fleet index lives in the lead engine's index buffers (its own plan uses none of them
   // during a fused round), sized for every plan's nodes and lanes
-  const long long Tmax = 1 + h->samples_issued + n_samples;
+  const long long Tmax = 1 + h->samples_issued + n_samples + F.extra;
   if ((long long)n * Tmax >= INT_MAX || (long long)n * F.bp >= INT_MAX)
     return fail(-1, "a fleet's node or lane slots exceed 2^31 (fewer plans per fleet)");
   if (int rc = ensure_index(h, (size_t)n * (size_t)Tmax, (size_t)n * (size_t)F.bp)) return rc;

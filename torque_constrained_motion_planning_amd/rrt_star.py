@@ -51,8 +51,8 @@ def _radius_value(radius):
 
 def rrt_star_force_aware(start, goal, distance, sample, extend, collision, torque_fn, dynam_fn,
                          radius, max_time=INF, max_iterations=INF, goal_probability=.2,
-                         *positional, retime=False, repair=False, informed=False,
-                         shortcut=False):
+                         *positional, connect=False, retime=False, repair=False,
+                         informed=False, shortcut=False):
     """rrt_star.py:151-211 -> (path, vels, accels, psg) or (None, None, None, None).
     The positional order is the reference's, then shortcut: a 13th positional argument is
     `informed` (rrt_star.py:151) and a 14th `shortcut`; retime and repair are keyword-only.
@@ -78,7 +78,10 @@ def rrt_star_force_aware(start, goal, distance, sample, extend, collision, torqu
     collision_fn on the device and the segments whose rows collide are put back on their
     checked chords (Engine.plan_repair) before the validation's verdict is used and before any
     retiming; a trajectory that still collides is dropped.  Engine loop with the package's own
-    dynamics fn only."""
+    dynamics fn only.
+    connect (no reference counterpart, off by default, keyword-only): after the last iteration
+    the goal is tried from the best nodes of the whole tree (Engine.plan_connect), which can find
+    a goal the loop missed or a cheaper parent for it; before the shortcut.  Engine loop only."""
     if positional:
         if len(positional) > 2:
             raise TypeError("rrt_star_force_aware() takes at most 14 positional arguments "
@@ -106,12 +109,16 @@ def rrt_star_force_aware(start, goal, distance, sample, extend, collision, torqu
     if k["distance"] and k["extend"] and k["collision"] and k["torque"]:
         res, _, _ = _rrt_engine(start, goal, distance, sample, extend, collision, torque_fn,
                                 dynam_fn, radius, max_iterations, goal_probability, k["dynam"],
-                                informed, shortcut, retime, repair)
+                                informed, shortcut, retime, repair, connect)
         return res
     if repair:
         raise NotImplementedError(
             "repair=True needs the package's own distance, extend, collision and torque "
             "callbacks (the trajectory is repaired in the engine's open plan)")
+    if connect:
+        raise NotImplementedError(
+            "connect=True needs the package's own distance, extend, collision and torque "
+            "callbacks (the candidates are ranked and checked on the device)")
     if shortcut:
         raise NotImplementedError(
             "shortcut=True needs the package's own distance, extend, collision and torque "
@@ -246,7 +253,7 @@ def _finish(eng, dynam_fn=None, torque_fn=None, retime=None, repair=None):
 # ---- engine loop ---------------------------------------------------------------------------
 def _rrt_engine(start, goal, distance, sample, extend, collision, torque_fn, dynam_fn, radius,
                 max_iterations, goal_probability, native_dynam=True, informed=False,
-                shortcut=False, retime=False, repair=False):
+                shortcut=False, retime=False, repair=False, connect=False):
     if max_iterations == INF:
         raise ValueError("max_iterations must be finite (the reference's time guard never "
                          "fires, rrt_star.py:159, so INF iterations never return)")
@@ -256,7 +263,7 @@ def _rrt_engine(start, goal, distance, sample, extend, collision, torque_fn, dyn
     goal = tuple(float(x) for x in goal)
     st = eng.plan_begin(start, goal, torque_fn.mode, torque_fn.payload_mass,
                         dynam_fn.execution_time if native_dynam else 0.0,
-                        max_nodes=max_iterations + 1, max_batch=1,
+                        max_nodes=max_iterations + 1 + bool(connect), max_batch=1,
                         weights=distance.weights, resolutions=extend.resolutions,
                         radius=_radius_value(radius), goal_probability=goal_probability)
     if st == _lib.PLAN_START_GOAL_COLLISION:
@@ -279,6 +286,8 @@ def _rrt_engine(start, goal, distance, sample, extend, collision, torque_fn, dyn
         if found and not goal_found and informed:
             goal_cost = eng.plan_goal()[1]
         goal_found = found
+    if connect:
+        eng.plan_connect()
     if shortcut:
         eng.plan_shortcut()
     return _finish(eng, None if native_dynam else dynam_fn, torque_fn, _retime_kw(retime),
@@ -289,7 +298,8 @@ def rrt_star_batched(start, goal, obstacles, torque_mode, payload_mass, executio
                      n_samples, batch=65536, seed=0, weights=None, resolutions=None,
                      radius=0.01, goal_probability=0.2, device=0, engine=None,
                      self_collisions=False, shortcut=False, shortcut_passes=1, retime=False,
-                     retime_max_scale=0.0, *, repair=False):
+                     retime_max_scale=0.0, *, repair=False, connect=False,
+                     connect_candidates=1024, connect_passes=1):
     """Engine-native batched frontier: n_samples Philox-drawn candidates, `batch` per round
     (self_collisions: the arm's self-collision pairs too, utils.py:3138-3149).
     shortcut: force-aware shortcutting of the path (Engine.plan_shortcut, shortcut_passes
@@ -304,6 +314,9 @@ def rrt_star_batched(start, goal, obstacles, torque_mode, payload_mass, executio
     repair: after the finish and before any retiming, collision repair of the min-jerk rows
     (Engine.plan_repair); raw["repair"] is the RepairResult, and a trajectory that still
     collides comes back as (None,)*4.
+    connect: after the rounds and before the shortcut, the goal is tried from the best
+    connect_candidates * connect_passes nodes of the whole tree (Engine.plan_connect); the tree
+    is allocated one node larger for it, and raw["connect"] is the ConnectResult.
 
     Returns ((path, vels, accels, psg) | (None,)*4, PlanResult, raw arrays)."""
     from .scene import mesh_pack, obstacle_array
@@ -312,16 +325,19 @@ def rrt_star_batched(start, goal, obstacles, torque_mode, payload_mass, executio
     eng.set_scene(obstacle_array(obstacles), mesh_pack(obstacles))
     eng.set_self_collision(self_collisions)
     st = eng.plan_begin(start, goal, torque_mode, payload_mass, execution_time,
-                        max_nodes=int(n_samples) + 1, max_batch=int(batch), seed=seed,
-                        weights=weights, resolutions=resolutions, radius=radius,
+                        max_nodes=int(n_samples) + 1 + bool(connect), max_batch=int(batch),
+                        seed=seed, weights=weights, resolutions=resolutions, radius=radius,
                         goal_probability=goal_probability)
     if st == _lib.PLAN_START_GOAL_COLLISION:
         return (None, None, None, None), None, None
     eng.plan_run(int(n_samples), int(batch))
+    cn = eng.plan_connect(connect_candidates, connect_passes) if connect else None
     sc = eng.plan_shortcut(passes=shortcut_passes) if shortcut else None
     res, r, raw = _finish(eng, retime=rt, repair={} if repair else None)
-    if shortcut or retime:
+    if shortcut or retime or connect:
         raw = dict(raw) if raw is not None else {}
+        if connect:
+            raw["connect"] = cn
         if shortcut:
             raw["shortcut"] = sc
         if retime:
