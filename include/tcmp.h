@@ -129,6 +129,58 @@ int tcmp_set_mesh_spheres(tcmp_handle* h, const double* spheres, int32_t n_mesh,
  * default, as in the reference planner (SELF_COLLISIONS = False, utils.py:56). */
 int tcmp_set_self_collision(tcmp_handle* h, int32_t enable);
 
+/* Bodies held by the gripper (get_collision_fn(..., attachments=[...]), utils.py:3165-3218: the
+ * attached bodies are assigned to their parent link at every configuration and tested against
+ * every obstacle; Grasp.get_attachment, utils.py:3363-3365, builds them).  n <= 4 convex hulls in
+ * their own (child) frames, in tcmp_set_meshes' layout, each of at most 64 vertices (so at most
+ * 124 facets and 186 edges).  parent_link: index into the ten moving collision links (0..6
+ * panda_link1..7, 7 panda_hand, 8 / 9 the fingers).  parent_from_child: n x 12, R row-major then
+ * p; the body's world pose at q is world_from_parent(q) * parent_from_child, world_from_parent
+ * being the collision model's link frame.  The tool frame is no collision link: the caller folds
+ * hand_from_tool = Trans(0, 0, 0.105) into parent_from_child.
+ * Depth of a held body against an obstacle (a box of tcmp_set_scene or a mesh of
+ * tcmp_set_meshes): the minimum overlap over the facet normals of both and the normalised cross
+ * products of their unit edge directions (squared cross norm below 1e-12 skipped), fp64 -- the
+ * definition tcmp_base_pd uses.  Held flag of a configuration: any depth >= 0.04.  No joint-limit
+ * test of its own, no test against the robot's own links (utils.py:3191 is a TODO) or among held
+ * bodies.
+ * With attachments set, tcmp_check_configs ORs the held flag into its flags, and every edge walk
+ * (tcmp_check_edges, tcmp_plan_round, tcmp_plan_run and its round graphs, tcmp_plan_shortcut,
+ * tcmp_shortcut_path, tcmp_plan_connect, tcmp_connect_nodes) and the rewiring end an edge at
+ * the first step whose held flag is set, as the sequential walk with that collision_fn does
+ * (n_steps unchanged).  tcmp_plan_begin tests start and goal with it.
+ * tcmp_plan_run_fused, tcmp_plan_run_group, tcmp_plan_run_shared, tcmp_plan_begin_many,
+ * tcmp_plan_repair, tcmp_repair_traj and tcmp_goal_search do not check held bodies: with
+ * attachments set they return -1 with a message naming the attachment and do nothing.
+ * n = 0 clears.  Replaces the previous set; keeps boxes, meshes and the self-collision setting.
+ * A set and a scene must fit a block's LDS together: the rewiring stages the arm's LDS (n x 160
+ * + 76,280 B for a box scene of n obstacles, n x 32 + 71,496 B with meshes or self-collision) and behind it
+ * 128 B per obstacle and 24 B per hull row (vertices, distinct facet normals and edge
+ * directions) within 137,720 B -- about 210 boxes with one 8-vertex box held, about 88 with four
+ * 64-vertex hulls.  tcmp_set_attachments, tcmp_set_scene, tcmp_set_meshes and
+ * tcmp_set_self_collision refuse (-1, with the figures) a change that would not fit, and change
+ * nothing then.
+ * Refused (-1) while a plan is open, that is from its tcmp_plan_begin to its tcmp_plan_finish or
+ * tcmp_plan_retrace (a finished plan's later stages take the set as it is then).  Validated (-1 otherwise): unit plane normals and every
+ * vertex inside every plane within 1e-9, edge rows in range, R^T R = I within 1e-9, det R > 0,
+ * parent_link in 0..9, the sizes above. */
+int tcmp_set_attachments(tcmp_handle* h, const tcmp_hulls* hulls, int32_t n,
+                         const int32_t* parent_link, const double* parent_from_child);
+
+/* Probe (utils.py:3165-3218, the attachments' pairwise_collision): the depth of every held body
+ * against every obstacle at n configurations, by the arithmetic the flags use and with no
+ * certificate applied.  pd: n x n_att x (n_box + n_mesh), obstacles in tcmp_base_pd's order. */
+int tcmp_attached_pd(tcmp_handle* h, const double* q, int64_t n, double* pd);
+
+/* Instrumentation of the held bodies' edge post-pass (no reference counterpart).  counts[4]:
+ * since the last tcmp_plan_begin (or tcmp_set_attachments), over every edge walk of the handle,
+ * the edges whose arm walk accepted a prefix, those of them the held bodies shortened, those
+ * they removed (n_safe' = 0); then the round graphs this handle has captured in its lifetime.
+ * ms (may be NULL): the device time of the post-pass kernel alone since the last
+ * tcmp_plan_begin, by events around its launches (0 with tcmp_set_timing off); it is part of
+ * tcmp_plan_result.ms_edges. */
+int tcmp_attach_stats(tcmp_handle* h, uint64_t* counts, double* ms);
+
 /* per-kernel-family device timing of plans (tcmp_plan_result.ms_*: hipEvents recorded around
  * each family, event nodes inside captured round graphs).  On by default; off records no
  * events, so a round graph holds kernel nodes only and ms_* stay 0 (queries run concurrently
@@ -155,7 +207,8 @@ int tcmp_check_configs(tcmp_handle* h, const double* q, int64_t n, int32_t* coll
  * (franka_ik_fast.py:78, panda_primitives.py:260 -> utils.py:2872-2880 body_collision ->
  * get_closest_points(max_distance=-0.04), :2833): every link of the robot body, i.e. the moving
  * links AND the static base panda_link0, penetration >= 0.04 m, no joint-limit test.
- * collides: n int32. */
+ * The robot against the obstacles only: bodies set with tcmp_set_attachments are not part of it
+ * (it is the grasp check, made before anything is held).  collides: n int32. */
 int tcmp_check_body(tcmp_handle* h, const double* q, int64_t n, int32_t* collides);
 
 /* Penetration depth of the static base panda_link0 (world = base frame) against each obstacle
@@ -822,6 +875,12 @@ int tcmp_plan_digest(tcmp_handle* h, uint64_t* digest, int64_t* n_nodes);
 /* debug: tree snapshot (cfg n x 7, cost n, parent n). */
 int tcmp_plan_tree(tcmp_handle* h, int64_t cap, double* cfg, double* cost, int32_t* parent,
                    int64_t* n);
+/* debug: the edge each node of the open plan's tree was inserted (or last rewired) on, rows as
+ * tcmp_plan_tree's: tgt (cap x 7) the extend target the edge from the parent was walked toward,
+ * meta (cap x 2) its (n_steps, n_safe) -- the node's configuration is the parent's after n_safe
+ * refine steps of n_steps toward tgt (rrt_star.py:90-98, safe_path_force_aware(extend(...))).
+ * The root's row is (its own configuration, 0, 0).  *n: the tree's node count. */
+int tcmp_plan_tree_edges(tcmp_handle* h, int64_t cap, double* tgt, int32_t* meta, int64_t* n);
 
 /* debug: the last round's nearest-neighbour step (rrt_star.py:171 for every lane): its nb
  * candidates (cand nb x 7), the chosen nearest node of each (nn, an index into the tree) and

@@ -26,6 +26,7 @@ EXPORTS = [
     "tcmp_synchronize",
     "tcmp_set_scene", "tcmp_set_meshes", "tcmp_set_mesh_lods", "tcmp_set_mesh_spheres", "tcmp_set_self_collision", "tcmp_set_timing", "tcmp_rne_batch", "tcmp_torque_ok", "tcmp_check_configs",
     "tcmp_check_body", "tcmp_base_pd",
+    "tcmp_set_attachments", "tcmp_attached_pd", "tcmp_attach_stats", "tcmp_plan_tree_edges",
     "tcmp_check_edges", "tcmp_nearest", "tcmp_minjerk", "tcmp_validate_traj",
     "tcmp_plan_begin", "tcmp_plan_round", "tcmp_plan_goal", "tcmp_plan_run", "tcmp_plan_finish",
     "tcmp_plan_retrace",
@@ -282,6 +283,13 @@ def load_library(path=LIB_PATH):
         if hasattr(L, "tcmp_set_mesh_spheres"):  # absent from A/B builds of older sources
             L.tcmp_set_mesh_spheres.argtypes = [vp, _dp, ctypes.c_int32, ctypes.c_int32]
         L.tcmp_set_self_collision.argtypes = [vp, ctypes.c_int32]
+        if hasattr(L, "tcmp_set_attachments"):  # absent from A/B builds of older sources
+            L.tcmp_set_attachments.argtypes = [vp, ctypes.POINTER(Hulls), ctypes.c_int32, _i32p, _dp]
+            L.tcmp_attached_pd.argtypes = [vp, _dp, ctypes.c_int64, _dp]
+            L.tcmp_attach_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64),
+                                            ctypes.POINTER(ctypes.c_double)]
+            L.tcmp_plan_tree_edges.argtypes = [vp, ctypes.c_int64, _dp, _i32p,
+                                               ctypes.POINTER(ctypes.c_int64)]
         if hasattr(L, "tcmp_set_timing"):  # absent from A/B builds of older sources
             L.tcmp_set_timing.argtypes = [vp, ctypes.c_int32]
         L.tcmp_rne_batch.argtypes = [vp, _dp, _dp, _dp, ctypes.c_int64, ctypes.c_double, _dp]
@@ -621,6 +629,55 @@ class Engine:
         if enable != self._self_coll:
             self._check(self.L.tcmp_set_self_collision(self.h, int(enable)))
             self._self_coll = enable
+
+    def set_attachments(self, hulls=(), parent_link=(), parent_from_child=()):
+        """Bodies held by the gripper for every later collision check (tcmp_set_attachments).
+        hulls: one (verts (V, 3), planes (F, 4), edges (E, 4)) per body in its own frame, as
+        hull.hull_data returns them; parent_link: index into the ten moving collision links
+        (COLLISION_LINK_NAMES order, 7 = panda_hand); parent_from_child: (n, 12) rows (R
+        row-major, p) or (n, 4, 4).  No hulls: clears."""
+        self._need("tcmp_set_attachments")
+        hulls = list(hulls)
+        n = len(hulls)
+        if n == 0:
+            self._check(self.L.tcmp_set_attachments(self.h, None, 0, None, None))
+            self._n_att = 0
+            return
+        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)  # noqa: E731
+        ip = lambda a: a.ctypes.data_as(_i32p)  # noqa: E731
+        v = [np.asarray(h[0], dtype=np.float64).reshape(-1, 3) for h in hulls]
+        f = [np.asarray(h[1], dtype=np.float64).reshape(-1, 4) for h in hulls]
+        e = [np.asarray(h[2], dtype=np.int32).reshape(-1, 4) for h in hulls]
+        off = lambda xs: i32(np.concatenate([[0], np.cumsum([len(x) for x in xs])]))  # noqa: E731
+        a = (np.ascontiguousarray(np.concatenate(v)), off(v), np.ascontiguousarray(np.concatenate(f)),
+             off(f), i32(np.concatenate(e)), off(e))
+        H = Hulls(_d(a[0]), ip(a[1]), _d(a[2]), ip(a[3]), ip(a[4]), ip(a[5]))
+        link = i32(np.asarray(parent_link).reshape(-1))
+        pfc = np.ascontiguousarray(pose_rows(parent_from_child))
+        if len(link) != n or len(pfc) != n:
+            raise ValueError("one parent_link and one parent_from_child per hull")
+        self._check(self.L.tcmp_set_attachments(self.h, ctypes.byref(H), n, ip(link), _d(pfc)))
+        self._n_att = n
+
+    def attached_pd(self, q):
+        """The depth of every held body against every box, then every mesh, at q (n, 7), no
+        certificate applied (tcmp_attached_pd) -> (n, n_att, n_box + n_mesh)."""
+        self._need("tcmp_attached_pd")
+        q = _rows(q, "q")
+        out = np.zeros((len(q), getattr(self, "_n_att", 0), getattr(self, "_n_scene", 0)))
+        self._check(self.L.tcmp_attached_pd(self.h, _d(q), len(q), _d(out) if out.size else None))
+        return out
+
+    def attach_stats(self):
+        """tcmp_attach_stats: dict(edges, shortened, removed) of the held bodies' edge post-pass
+        since the last plan_begin, graph_captures of this engine's lifetime, and ms, the
+        post-pass kernel's device time since the last plan_begin."""
+        self._need("tcmp_attach_stats")
+        c = (ctypes.c_uint64 * 4)()
+        ms = ctypes.c_double(0.0)
+        self._check(self.L.tcmp_attach_stats(self.h, c, ctypes.byref(ms)))
+        return dict(edges=int(c[0]), shortened=int(c[1]), removed=int(c[2]),
+                    graph_captures=int(c[3]), ms=ms.value)
 
     def collides(self, q):
         q = _rows(q, "q")
@@ -1005,6 +1062,17 @@ class Engine:
                                           par.ctypes.data_as(_i32p), ctypes.byref(n)))
         m = min(cap, n.value)
         return cfg[:m], cost[:m], par[:m], n.value
+
+    def plan_tree_edges(self, cap):
+        """(tgt (n, 7), meta (n, 2): n_steps, n_safe) of the open plan's nodes: the edge each was
+        inserted or last rewired on (tcmp_plan_tree_edges)."""
+        self._need("tcmp_plan_tree_edges")
+        tgt = np.zeros((cap, 7)); meta = np.zeros((cap, 2), dtype=np.int32)
+        n = ctypes.c_int64(0)
+        self._check(self.L.tcmp_plan_tree_edges(self.h, int(cap), _d(tgt),
+                                                meta.ctypes.data_as(_i32p), ctypes.byref(n)))
+        m = min(cap, n.value)
+        return tgt[:m], meta[:m]
 
     def plan_debug_round(self, cap):
         """The last round's (candidates, nearest index, exact score, snapshot size)."""

@@ -646,6 +646,8 @@ __global__ __launch_bounds__(256, TCMP_EDGE_MINW) void k_edges(EdgeJob J, const 
   }
 }
 
+#include "tcmp_attach.h"
+
 // ------------------------------------------------------------------------------------------
 // rewire (rrt_star.py:183-192): neighbours of each new node within `radius` among the
 // round's snapshot, visited in index order; reparent when cheaper and the edge is safe.
@@ -700,11 +702,15 @@ __global__ __launch_bounds__(256) void k_rewire_scan(const PlanParams* __restric
   rewire_scan_block(Pd, st, tr, rwlist, nbr, ncount, blockIdx.x);
 }
 
-template <bool MESH>
+// ATT: held bodies are set (tcmp_set_attachments) -- each step that passes the arm's check also
+// takes the held flag (att_flag), its hulls and obstacle records staged behind the arm's LDS
+// (att_off doubles into it).  ATT = false is the code without them.
+template <bool MESH, bool ATT = false>
 __device__ __forceinline__ void rewire_apply_block(const PlanParams* __restrict__ Pd, DevState* st,
                                                    const Tree& tr, const int* rwlist,
                                                    const int* nbr, const int* ncount,
-                                                   const Scene& sc_g, const Geo& g_g, int blk) {
+                                                   const Scene& sc_g, const Geo& g_g, int blk,
+                                                   const AttSet* att = nullptr, int att_off = 0) {
   const PlanParams P = *Pd;
   extern __shared__ double tcmp_lds[];
   Scene sc;
@@ -718,6 +724,8 @@ __device__ __forceinline__ void rewire_apply_block(const PlanParams* __restrict_
   const bool act = t < R && ncount[t] > 0;
   if (!__syncthreads_or(act)) return;
   stage_lds<!MESH>(sc_g, g_g, tcmp_lds, sc, g);
+  AttLds al{};
+  if constexpr (ATT) al = att_stage(*att, sc_g, tcmp_lds + att_off);
   if (__ballot(act) == 0) return;  // wave-uniform
   const long long me = act ? rwlist[t] : 0;
   double qn[7];
@@ -777,6 +785,9 @@ __device__ __forceinline__ void rewire_apply_block(const PlanParams* __restrict_
       const bool lim = alive && limits_violated(qq);
       const bool coll = collides_wave<MESH>(cq, sq, alive && !lim, sc, g, ss) || lim;
       bool ok = alive && !coll;
+      if constexpr (ATT) {
+        if (ok) ok = !att_flag(cq, sq, *att, al, sc_g);
+      }
       if (ok && P.torque_mode != TCMP_TORQUE_BASE) {
         const double z[7] = {0, 0, 0, 0, 0, 0, 0};
         ok = P.torque_mode == TCMP_TORQUE_DYN ? torque_ok_dyn<false>(cq, sq, z, z, P.mass)
@@ -815,6 +826,14 @@ __global__ __launch_bounds__(256) void k_rewire_apply(const PlanParams* __restri
                                                       const int* rwlist, const int* nbr,
                                                       const int* ncount, Scene sc_g, Geo g_g) {
   rewire_apply_block<MESH>(Pd, st, tr, rwlist, nbr, ncount, sc_g, g_g, blockIdx.x);
+}
+// the rewire with held bodies set: launched in k_rewire_apply's place only then
+template <bool MESH>
+__global__ __launch_bounds__(256) void k_rewire_apply_att(const PlanParams* __restrict__ Pd, DevState* st, Tree tr,
+                                                          const int* rwlist, const int* nbr,
+                                                          const int* ncount, Scene sc_g, Geo g_g,
+                                                          AttSet A, int att_off) {
+  rewire_apply_block<MESH, true>(Pd, st, tr, rwlist, nbr, ncount, sc_g, g_g, blockIdx.x, &A, att_off);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1444,7 +1463,7 @@ struct Stream {
 // F_NNSCAN times the k_nearest_wave launch alone (inside F_NEAREST, not added to totals)
 // F_EDGE_PREP: the edge order's counting sort and k_edge_records, so that F_EDGES times
 // k_edges alone (its roofline divides by that time)
-enum Fam { F_NEAREST = 0, F_EDGES, F_INSERT, F_REWIRE, F_FINISH, F_NNSCAN, F_EDGE_PREP, F_COUNT };
+enum Fam { F_NEAREST = 0, F_EDGES, F_INSERT, F_REWIRE, F_FINISH, F_NNSCAN, F_EDGE_PREP, F_ATT, F_COUNT };  // F_ATT: k_att_edges alone (inside F_EDGES)
 
 // one family's span between two recorded events; adjacent families share the boundary event
 // (one record per boundary: each record is an event node of ~5 us in a round graph)
@@ -1671,6 +1690,16 @@ struct tcmp_handle {
   DBuf<int> cn_nsafe, cn_nsteps;
   DBuf<unsigned char> cn_state, cn_tmp;
   long long extra_nodes = 0;
+  // held bodies (tcmp_set_attachments, tcmp_attach.h): the set as the kernels take it (n = 0:
+  // none), its hull rows on the device, and a generation number every call bumps (round-graph key)
+  AttSet att{};
+  DBuf<double> att_geo;
+  long long att_gen = 0;
+  bool att_locked = false;  // a plan is growing: from its begin to its first finish or retrace
+  // k_att_edges' counts [edges it saw with an accepted prefix, shortened, removed], zeroed at
+  // tcmp_plan_begin (tcmp_attach_stats)
+  DBuf<unsigned long long> att_stats;
+  long long graph_captures = 0;  // round graphs captured and instantiated by this handle
   int edge_split = 4; // most lanes per edge in small rounds (environment TCMP_EDGE_SPLIT=1/2/4)
   int edge_wps = 2;    // k_edges' persistent grid, blocks per CU (environment TCMP_EDGE_WPS=1/2)
 
@@ -2092,6 +2121,75 @@ __global__ __launch_bounds__(256) void k_edge_order_keys(const PlanParams* __res
   edge_order_block(Pd, cfg, nn, cand, nb, bins, hist, blockIdx.x);
 }
 
+// ---- held bodies (tcmp_attach.h): the launches that follow the arm's, only when some are set
+// the set with the scene's current obstacle counts; fails when its LDS does not fit a block
+// (base_lds: the arm's LDS ahead of it in the ATT rewire, whose limit is the arm kernels' own)
+int att_args(const tcmp_handle* h, AttSet* A, unsigned base_lds = 0) {
+  *A = h->att;
+  A->n_box = h->n_box;
+  A->n_mesh = h->n_mesh;
+  const unsigned limit = base_lds ? (unsigned)stage_lds_bytes(kMaxObstacles) : kAttLdsLimit;
+  if (base_lds + att_lds_bytes(*A) > limit)  // (att_fits refused this combination where it was set)
+    return fail(-1, "the attachments' hulls and the scene's records do not fit the LDS of a block");
+  return 0;
+}
+
+// Whether a set of held bodies and a scene fit together: the ATT rewire stages the arm's LDS
+// (stage_lds_bytes / stage_lds_bytes_lean of the scene) and behind it 128 B per obstacle record
+// and 24 B per hull row, within the arm kernels' own limit stage_lds_bytes(kMaxObstacles).  The
+// setters (tcmp_set_attachments, tcmp_set_scene, tcmp_set_meshes, tcmp_set_self_collision) ask
+// before they change anything, so no round can meet a combination that does not fit.
+int att_fits(const tcmp_handle* h, const AttSet& set, int n_box, int n_mesh, int self_coll) {
+  if (set.n == 0) return 0;
+  AttSet A = set;
+  A.n_box = n_box;
+  A.n_mesh = n_mesh;
+  const int n_obs = n_box + n_mesh;
+  const unsigned arm = (n_mesh > 0 || self_coll) ? stage_lds_bytes_lean(n_obs) : stage_lds_bytes(n_obs);
+  const unsigned base = (arm + 7u) & ~7u, att = att_lds_bytes(A);
+  if (att > kAttLdsLimit || base + att > (unsigned)stage_lds_bytes(kMaxObstacles))
+    return fail(-1, "attachments and scene do not fit a block's LDS together: " +
+                        std::to_string(n_obs) + " obstacles take " + std::to_string(base) +
+                        " B for the arm and, with " + std::to_string(A.rows) + " hull rows, " +
+                        std::to_string(att) + " B for the held bodies, of " +
+                        std::to_string(stage_lds_bytes(kMaxObstacles)) +
+                        " B (fewer obstacles, or smaller or fewer held hulls)");
+  return 0;
+}
+
+// the entry points that do not take held bodies refuse them: status -1, nothing done
+int att_refuse(const tcmp_handle* h, const char* entry) {
+  if (!h || h->att.n == 0) return 0;
+  return fail(-1, std::string(entry) + " does not check held bodies: an attachment is set on the "
+                      "handle (tcmp_set_attachments with n = 0 clears it)");
+}
+
+// ORs the held flags of n configurations (rows of 8) into the flags k_check_configs wrote
+int launch_att_configs(tcmp_handle* h, const double* q, long long n, int* collides) {
+  if (h->att.n == 0 || n <= 0) return 0;
+  AttSet A;
+  if (int rc = att_args(h, &A)) return rc;
+  hipLaunchKernelGGL(k_att_configs, dim3(grid_for(n, 256)), dim3(256), att_lds_bytes(A), h->stream,
+                     q, n, h->scene(), A, collides);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// the edge post-pass behind k_edges: every caller of launch_edges gets it
+int launch_att_edges(tcmp_handle* h, DevState* st, const EdgeJob& J) {
+  if (h->att.n == 0) return 0;
+  AttSet A;
+  if (int rc = att_args(h, &A)) return rc;
+  const long long want = ((long long)J.n * kAttLanes + 255) / 256;
+  const long long blocks = std::max<long long>(1, std::min<long long>(want, 8LL * h->cu_count));
+  const hipEvent_t e0 = h->mark();
+  hipLaunchKernelGGL(k_att_edges, dim3((unsigned)blocks), dim3(256), att_lds_bytes(A), h->stream, J,
+                     h->scene(), A, st, h->att_stats.p);
+  HIPCHK(hipGetLastError());
+  h->span(F_ATT, e0, h->mark());
+  return 0;
+}
+
 // reset_counter = false: the plan's k_nn_home already cleared the work counter
 // kernel_begin (nullable): an event recorded between k_edge_records and k_edges (timing on)
 // st: the state the launch counts into (the plan's, or the shortcut pass's scratch state)
@@ -2124,7 +2222,7 @@ int launch_edges(tcmp_handle* h, DevState* st, const EdgeJob& J, const PlanParam
   hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), lds_bytes(h), h->stream, J, dP,
                      h->scene(), h->geo(), st);
   HIPCHK(hipGetLastError());
-  return 0;
+  return launch_att_edges(h, st, J);
 }
 
 PlanParams default_params() {
@@ -2282,6 +2380,10 @@ int tcmp_create(int device, tcmp_handle** out) {
                           (const void*)k_debug_pair_pd<false>, (const void*)k_debug_pair_pd<true>,
                           (const void*)k_rewire_apply<false>, (const void*)k_rewire_apply<true>})
       HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
+    for (const void* k : {(const void*)k_rewire_apply_att<false>, (const void*)k_rewire_apply_att<true>})
+      HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
+    for (const void* k : {(const void*)k_att_configs, (const void*)k_att_pd, (const void*)k_att_edges})
+      HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kAttLdsLimit));
     if ((rc = fleet_lds_limits())) return rc;
     if ((rc = repair_lds_limits())) return rc;
     if ((rc = goal_lds_limits())) return rc;
@@ -2796,6 +2898,7 @@ int tcmp_set_scene(tcmp_handle* h, const double* obb, int32_t n_obs) {
     const double* s = obb + 15 * o;
     if (!(s[12] >= 0 && s[13] >= 0 && s[14] >= 0)) return fail(-1, "negative half extent");
   }
+  if (int rc = att_fits(h, h->att, n_obs, h->n_mesh, h->self_coll)) return rc;
   h->box15.assign(obb, obb + 15 * (size_t)n_obs);
   h->n_box = n_obs;
   return upload_scene(h);
@@ -2810,6 +2913,7 @@ int tcmp_set_meshes(tcmp_handle* h, const double* verts, const int32_t* vert_off
   if (h->n_box + n_mesh > kMaxObstacles)
     return fail(-1, "too many obstacles (" + std::to_string(h->n_box + n_mesh) + " > " +
                         std::to_string(kMaxObstacles) + ", the LDS-staged scene limit)");
+  if (int rc = att_fits(h, h->att, h->n_box, n_mesh, h->self_coll)) return rc;
   const tcmp_hulls H{verts, vert_off, planes, plane_off, edges, edge_off};
   if (n_mesh > 0)
     if (int rc = check_hulls(&H, n_mesh, "mesh")) return rc;
@@ -2892,9 +2996,158 @@ int tcmp_set_self_collision(tcmp_handle* h, int32_t enable) {
   TCMP_ENTER(h);
   const int on = enable ? 1 : 0;
   if (on == h->self_coll) return 0;
+  if (int rc = att_fits(h, h->att, h->n_box, h->n_mesh, on)) return rc;
   h->self_coll = on;
   if (int rc = upload_meshes(h)) return rc;
   return upload_scene(h);
+}
+
+int tcmp_set_attachments(tcmp_handle* h, const tcmp_hulls* hulls, int32_t n,
+                         const int32_t* parent_link, const double* parent_from_child) {
+  TCMP_ENTER(h);
+  if (h->att_locked)
+    return fail(-1, "attachments cannot change while a plan is open (between tcmp_plan_begin and "
+                    "the plan's tcmp_plan_finish or tcmp_plan_retrace)");
+  if (n < 0 || n > kAttMax)
+    return fail(-1, "attachment count out of range (at most " + std::to_string(kAttMax) + ")");
+  if (n == 0) {
+    h->att = AttSet{};
+    ++h->att_gen;
+    return 0;
+  }
+  if (!parent_link || !parent_from_child) return fail(-1, "null attachment placement array");
+  if (int rc = check_hulls(hulls, n, "attachment")) return rc;
+  AttSet A{};
+  A.n = n;
+  std::vector<double> rows;  // of 3
+  auto parallel = [](const double* a, const double* b) {
+    return a[1] * b[2] - a[2] * b[1] == 0.0 && a[2] * b[0] - a[0] * b[2] == 0.0 &&
+           a[0] * b[1] - a[1] * b[0] == 0.0;
+  };
+  for (int m = 0; m < n; ++m) {
+    const std::string who = "attachment " + std::to_string(m);
+    const int v0 = hulls->vert_off[m], nv = hulls->vert_off[m + 1] - v0;
+    const int f0 = hulls->plane_off[m], nf = hulls->plane_off[m + 1] - f0;
+    const int e0 = hulls->edge_off[m], ne = hulls->edge_off[m + 1] - e0;
+    if (nv > kAttMaxV || nf > kAttMaxF || ne > kAttMaxE)
+      return fail(-1, who + ": hull too large (at most " + std::to_string(kAttMaxV) + " vertices, " +
+                          std::to_string(kAttMaxF) + " facets, " + std::to_string(kAttMaxE) + " edges)");
+    if (parent_link[m] < 0 || parent_link[m] >= TCMP_NLINKS)
+      return fail(-1, who + ": parent_link out of range (0.." + std::to_string(TCMP_NLINKS - 1) + ")");
+    const double* V = hulls->verts + 3 * (size_t)v0;
+    const double* P = hulls->planes + 4 * (size_t)f0;
+    for (int i = 0; i < 3 * nv; ++i)
+      if (!std::isfinite(V[i])) return fail(-1, who + ": non-finite vertex");
+    for (int f = 0; f < nf; ++f) {
+      const double* p = P + 4 * f;
+      if (!(fabs(p[0] * p[0] + p[1] * p[1] + p[2] * p[2] - 1.0) <= 1e-9))
+        return fail(-1, who + ": plane " + std::to_string(f) + " has no unit normal");
+      for (int v = 0; v < nv; ++v)
+        if (!(p[0] * V[3 * v] + p[1] * V[3 * v + 1] + p[2] * V[3 * v + 2] - p[3] <= 1e-9))
+          return fail(-1, who + ": vertex " + std::to_string(v) + " lies outside plane " +
+                              std::to_string(f));
+    }
+    const double* T = parent_from_child + 12 * (size_t)m;
+    for (int i = 0; i < 12; ++i)
+      if (!std::isfinite(T[i])) return fail(-1, who + ": non-finite parent_from_child");
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 3; ++j) {
+        const double d = T[i] * T[j] + T[3 + i] * T[3 + j] + T[6 + i] * T[6 + j];
+        if (!(fabs(d - (i == j ? 1.0 : 0.0)) <= 1e-9))
+          return fail(-1, who + ": parent_from_child is not a rotation (R^T R differs from I)");
+      }
+    const double det = T[0] * (T[4] * T[8] - T[5] * T[7]) - T[1] * (T[3] * T[8] - T[5] * T[6]) +
+                       T[2] * (T[3] * T[7] - T[4] * T[6]);
+    if (!(det > 0)) return fail(-1, who + ": parent_from_child is a reflection, not a rotation");
+    AttBody& B = A.b[m];
+    B.link = parent_link[m];
+    for (int i = 0; i < 12; ++i) A.pfc[m][i] = T[i];
+    // vertices; the bounding ball about the centre of their box
+    B.v0 = (int)(rows.size() / 3);
+    B.nv = nv;
+    rows.insert(rows.end(), V, V + 3 * (size_t)nv);
+    double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY}, r2 = 0;
+    for (int v = 0; v < nv; ++v)
+      for (int k = 0; k < 3; ++k) {
+        lo[k] = std::min(lo[k], V[3 * v + k]);
+        hi[k] = std::max(hi[k], V[3 * v + k]);
+      }
+    for (int k = 0; k < 3; ++k) A.ball[m][k] = 0.5 * (lo[k] + hi[k]);
+    for (int v = 0; v < nv; ++v) {
+      double d2 = 0;
+      for (int k = 0; k < 3; ++k) d2 += (V[3 * v + k] - A.ball[m][k]) * (V[3 * v + k] - A.ball[m][k]);
+      r2 = std::max(r2, d2);
+    }
+    A.ball[m][3] = sqrt(r2) * (1.0 + 1e-12);
+    // facet normals and unit edge directions; one of several exactly parallel rows is enough (an
+    // axis and its negative give the same overlap, bit for bit)
+    B.f0 = (int)(rows.size() / 3);
+    for (int f = 0; f < nf; ++f) {
+      const double* p = P + 4 * f;
+      bool dup = false;
+      for (int g = B.f0; g < (int)(rows.size() / 3) && !dup; ++g) dup = parallel(p, &rows[3 * (size_t)g]);
+      if (!dup) rows.insert(rows.end(), p, p + 3);
+    }
+    B.nf = (int)(rows.size() / 3) - B.f0;
+    B.e0 = (int)(rows.size() / 3);
+    for (int e = 0; e < ne; ++e) {
+      const int* q = hulls->edges + 4 * (size_t)(e0 + e);
+      const double* a = V + 3 * q[0];
+      const double* b = V + 3 * q[1];
+      double d[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]};
+      const double l = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+      if (!(l > 0)) return fail(-1, who + ": edge " + std::to_string(e) + " has no length");
+      for (int k = 0; k < 3; ++k) d[k] /= l;
+      bool dup = false;
+      for (int g = B.e0; g < (int)(rows.size() / 3) && !dup; ++g) dup = parallel(d, &rows[3 * (size_t)g]);
+      if (!dup) rows.insert(rows.end(), d, d + 3);
+    }
+    B.ne = (int)(rows.size() / 3) - B.e0;
+  }
+  A.rows = (int)(rows.size() / 3);
+  if (int rc = att_fits(h, A, h->n_box, h->n_mesh, h->self_coll)) return rc;
+  if (int rc = h->att_stats.ensure(4)) return rc;
+  HIPCHK(hipMemsetAsync(h->att_stats.p, 0, 4 * sizeof(unsigned long long), h->stream));
+  if (int rc = upload(h, h->att_geo, rows.data(), rows.size())) return rc;
+  if (int rc_s = sync_stream(h)) return rc_s;
+  A.geo = h->att_geo.p;
+  h->att = A;
+  ++h->att_gen;
+  return 0;
+}
+
+int tcmp_attached_pd(tcmp_handle* h, const double* q, int64_t n, double* pd) {
+  TCMP_ENTER(h);
+  if (h->att.n == 0) return fail(-1, "no attachments set (tcmp_set_attachments first)");
+  const int no = h->n_box + h->n_mesh;
+  if (n < 0 || (n > 0 && no > 0 && (!q || !pd))) return fail(-1, "bad arguments");
+  const long long total = (long long)n * h->att.n * no;
+  if (total == 0) return 0;
+  AttSet A;
+  if (int rc = att_args(h, &A)) return rc;
+  int rc = upload7(h, h->s0, q, n);
+  rc = rc ? rc : h->s1.ensure((size_t)total);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_att_pd, dim3(grid_for(total, 256)), dim3(256), att_lds_bytes(A), h->stream,
+                     h->s0.p, (long long)n, h->scene(), A, h->s1.p);
+  HIPCHK(hipGetLastError());
+  if (int rc2 = download(h, pd, h->s1.p, (size_t)total)) return rc2;
+  return sync_stream(h);
+}
+
+int tcmp_attach_stats(tcmp_handle* h, uint64_t* counts, double* ms) {
+  TCMP_ENTER(h);
+  if (!counts) return fail(-1, "null counts");
+  unsigned long long c[4] = {0, 0, 0, 0};
+  if (h->att_stats.p) {
+    if (int rc = download(h, c, h->att_stats.p, 4)) return rc;
+    if (int rc_s = sync_stream(h)) return rc_s;
+  }
+  h->collect_events();
+  for (int i = 0; i < 3; ++i) counts[i] = c[i];
+  counts[3] = (uint64_t)h->graph_captures;
+  if (ms) *ms = h->ms[F_ATT];
+  return 0;
 }
 
 int tcmp_set_timing(tcmp_handle* h, int32_t enable) {
@@ -2982,6 +3235,7 @@ int tcmp_check_configs(tcmp_handle* h, const double* q, int64_t n, int32_t* coll
   hipLaunchKernelGGL(h->mesh_kernels() ? k_check_configs<true> : k_check_configs<false>, dim3(grid_for(n, 256)), dim3(256), lds_bytes(h), h->stream, h->s0.p,
                      (long long)n, h->scene(), h->geo(), h->i0.p, 0);
   HIPCHK(hipGetLastError());
+  if (int rc = launch_att_configs(h, h->s0.p, n, h->i0.p)) return rc;
   if (int rc = download(h, collides, h->i0.p, (size_t)n)) return rc;
   return sync_stream(h);
 }
@@ -3369,6 +3623,7 @@ int plan_begin_launch(tcmp_handle* h, const tcmp_plan_cfg* cfg, tcmp_plan_result
   h->fused_plans = 0;
   h->launches_scan = 0;
   h->graph_launches = 0;
+  if (h->att.n) HIPCHK(hipMemsetAsync(h->att_stats.p, 0, 4 * sizeof(unsigned long long), h->stream));
   // the finish's buffers, sized here so that tcmp_plan_finish needs one host wait: waypoints
   // (bounded by the chain's total n_safe; generous, checked on the device) and trajectory
   // rows K = (W - 1) * floor(exec_time * 1000 / W) < exec_time * 1000 (k_retrace)
@@ -3421,6 +3676,9 @@ int plan_begin_launch(tcmp_handle* h, const tcmp_plan_cfg* cfg, tcmp_plan_result
                      reinterpret_cast<const double*>(h->dpin.p + offsetof(tcmp_handle::Pin, sg)), 2LL, h->scene(),
                      h->geo(), h->i0.p, 0);
   HIPCHK(hipGetLastError());
+  if (int rc2 = launch_att_configs(h, reinterpret_cast<const double*>(h->dpin.p + offsetof(tcmp_handle::Pin, sg)),
+                                   2, h->i0.p))
+    return rc2;
   HIPCHK(hipMemcpyAsync(pn.coll, h->i0.p, 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
   return 0;
 }
@@ -3432,6 +3690,7 @@ int plan_begin_complete(tcmp_handle* h, tcmp_plan_result* result) {
   result->n_nodes = 1;
   result->status = (pn.coll[0] || pn.coll[1]) ? TCMP_PLAN_START_GOAL_COLLISION : TCMP_PLAN_OK;
   if (result->status) h->plan_open = false;
+  h->att_locked = h->plan_open;  // until the plan's finish or retrace (plan_finish_launch)
   return 0;
 }
 
@@ -3449,6 +3708,8 @@ int tcmp_plan_begin_many(tcmp_handle* const* hs, int32_t n, const tcmp_plan_cfg*
                          tcmp_plan_result* results) {
   Entry entry;
   if (!hs || n < 1 || !cfgs || !results) return fail(-1, "bad arguments");
+  for (int q = 0; q < n; ++q)
+    if (int rc = att_refuse(hs[q], "tcmp_plan_begin_many")) return rc;
   for (int q = 0; q < n; ++q) {
     int rc = set_dev(hs[q]);
     rc = rc ? rc : plan_begin_launch(hs[q], cfgs + q, results + q);
@@ -3497,6 +3758,8 @@ static unsigned long long round_graph_key(const tcmp_handle* h, long long n_samp
   mix((unsigned long long)h->timing);
   mix((unsigned long long)h->edge_wps);
   mix((unsigned long long)h->cu_count);
+  mix((unsigned long long)h->att.n);  // held bodies: their count and the set's generation
+  mix((unsigned long long)h->att_gen);
   for (const void* p : {(const void*)h->cfg.p, (const void*)h->tgt.p, (const void*)h->parent.p,
                         (const void*)h->meta.p, (const void*)h->cand.p, (const void*)h->last.p,
                         (const void*)h->cgoal.p, (const void*)h->nn.p, (const void*)h->nsafe.p,
@@ -3631,8 +3894,19 @@ static int round_finish(tcmp_handle* h, int32_t nb) {
   hipLaunchKernelGGL(k_rewire_scan, dim3(grid_for(nb, 256)), dim3(256), 0, h->stream, h->dP, h->st,
                      tr, h->rwlist.p, h->nbr.p, h->ncount.p);
   HIPCHK(hipGetLastError());
-  hipLaunchKernelGGL(h->mesh_kernels() ? k_rewire_apply<true> : k_rewire_apply<false>, dim3(grid_for(nb, 256)), dim3(256), lds_bytes(h), h->stream, h->dP, h->st,
-                     tr, h->rwlist.p, h->nbr.p, h->ncount.p, h->scene(), h->geo());
+  if (h->att.n) {
+    // held bodies: the ATT instantiation, their LDS behind the arm's
+    const unsigned base = (lds_bytes(h) + 7u) & ~7u;
+    AttSet A;
+    if (int rc = att_args(h, &A, base)) return rc;
+    hipLaunchKernelGGL(h->mesh_kernels() ? k_rewire_apply_att<true> : k_rewire_apply_att<false>,
+                       dim3(grid_for(nb, 256)), dim3(256), base + att_lds_bytes(A), h->stream, h->dP,
+                       h->st, tr, h->rwlist.p, h->nbr.p, h->ncount.p, h->scene(), h->geo(), A,
+                       (int)(base / 8));
+  } else {
+    hipLaunchKernelGGL(h->mesh_kernels() ? k_rewire_apply<true> : k_rewire_apply<false>, dim3(grid_for(nb, 256)), dim3(256), lds_bytes(h), h->stream, h->dP, h->st,
+                       tr, h->rwlist.p, h->nbr.p, h->ncount.p, h->scene(), h->geo());
+  }
   HIPCHK(hipGetLastError());
   h->mark_end(F_REWIRE, e0);
   return 0;
@@ -3859,6 +4133,7 @@ class GroupExchange : public tcmp_dist::RoundExchange {
 
 int tcmp_plan_run_shared(tcmp_handle* h, tcmp_comm* c, int64_t n_samples, int32_t batch) {
   TCMP_ENTER(h);
+  if (int rc = att_refuse(h, "tcmp_plan_run_shared")) return rc;
   if (!c) return fail(-1, "null comm");
   const int W = tcmp_dist::world(c);
   if (W == 1) return tcmp_plan_run(h, n_samples, batch);
@@ -3870,6 +4145,8 @@ int tcmp_plan_run_shared(tcmp_handle* h, tcmp_comm* c, int64_t n_samples, int32_
 int tcmp_plan_run_group(tcmp_handle* const* hs, int32_t n, int64_t n_samples, int32_t batch) {
   Entry entry;  // the engines' threads below run inside this entry (they take no lock)
   if (!hs || n < 1) return fail(-1, "bad arguments");
+  for (int q = 0; q < n; ++q)
+    if (int rc = att_refuse(hs[q], "tcmp_plan_run_group")) return rc;
   if (n == 1) return tcmp_plan_run(hs[0], n_samples, batch);
   for (int q = 0; q < n; ++q) {
     if (!hs[q]) return fail(-1, "null handle");
@@ -3984,6 +4261,7 @@ int tcmp_plan_run(tcmp_handle* h, int64_t n_samples, int32_t batch) {
             hipGraphInstantiate(&h->rg.exec, g, nullptr, nullptr, 0) == hipSuccess) {
           h->rg.graph = g;
           h->rg.key = key;
+          ++h->graph_captures;
           h->rg.rounds = (int)(h->launches_nearest - launches);
           h->rg.scans = (int)(h->launches_scan - scans);
         } else {
@@ -4033,6 +4311,7 @@ static void finish_launch_traj(tcmp_handle* h) {
 static int plan_finish_launch(tcmp_handle* h, tcmp_plan_result* r, bool traj) {
   if (!r) return fail(-1, "null result");
   if (!h->plan_open) return fail(-1, "no open plan");
+  h->att_locked = false;  // the tree is done growing, whatever the finish returns
   memset(r, 0, sizeof(*r));
   r->first_fail = -1;
   h->fin_status = -1;  // (a repair or a retiming of the last finish's rows ends here)
@@ -4282,6 +4561,26 @@ int tcmp_plan_digest(tcmp_handle* h, uint64_t* digest, int64_t* n_nodes) {
   if (int rc_s = sync_stream(h)) return rc_s;
   *digest = d;
   *n_nodes = nn;
+  return 0;
+}
+
+int tcmp_plan_tree_edges(tcmp_handle* h, int64_t cap, double* tgt, int32_t* meta, int64_t* n) {
+  TCMP_ENTER(h);
+  if (!n) return fail(-1, "null n");
+  long long nn = 0;
+  HIPCHK(hipMemcpyAsync(&nn, &h->st->n_nodes, sizeof(nn), hipMemcpyDeviceToHost, h->stream));
+  if (int rc_s = sync_stream(h)) return rc_s;
+  *n = nn;
+  const long long m = std::min<long long>(nn, cap);
+  if (m <= 0) return 0;
+  std::vector<double> tmp((size_t)m * 8);
+  if (int rc = download(h, tmp.data(), h->tgt.p, tmp.size())) return rc;
+  if (meta)
+    if (int rc = download(h, reinterpret_cast<int2*>(meta), h->meta.p, m)) return rc;
+  if (int rc_s = sync_stream(h)) return rc_s;
+  if (tgt)
+    for (long long i = 0; i < m; ++i)
+      for (int k = 0; k < 7; ++k) tgt[7 * i + k] = tmp[8 * i + k];
   return 0;
 }
 

@@ -805,6 +805,8 @@ int tcmp_plan_run_fused(tcmp_handle* const* hs, int32_t n, int64_t n_samples, in
   if (!hs || n < 1 || n > kFleetMax) return fail(-1, "fused rounds take 1..31 engines");
   tcmp_handle* h = hs[0];
   TCMP_ENTER(h);
+  for (int q = 0; q < n; ++q)
+    if (int rc = att_refuse(hs[q], "tcmp_plan_run_fused")) return rc;
   if (batch < 1) return fail(-1, "batch size out of range");
   long long F_extra = 0;  // the most nodes a goal connection appended to one of the plans
   for (int q = 0; q < n; ++q) {

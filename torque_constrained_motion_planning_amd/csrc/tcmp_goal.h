@@ -310,6 +310,7 @@ int tcmp_goal_search(tcmp_handle* h, const double* poses, int32_t n_pose, const 
                      double* dist_out, double* headroom_out, int32_t* id_out,
                      tcmp_goal_stats* stats, double* ms) {
   TCMP_ENTER(h);
+  if (int rc = att_refuse(h, "tcmp_goal_search")) return rc;
   if (!poses || !free_q7 || !ref || n_pose < 1 || n_free < 1 || max_out < 1 || max_out > 256)
     return fail(-1, "bad arguments");
   if ((long long)n_pose * n_free * 8 >= (1ll << 31)) return fail(-1, "n_pose * n_free * 8 >= 2^31");

@@ -295,6 +295,7 @@ int tcmp_repair_traj(tcmp_handle* h, const double* waypoints, int64_t n_wp, int6
                      const tcmp_repair_cfg* cfg, double* q, double* qd, double* qdd, int32_t* gates,
                      tcmp_repair_result* res) {
   TCMP_ENTER(h);
+  if (int rc = att_refuse(h, "tcmp_repair_traj")) return rc;
   if (!res || !waypoints) return fail(-1, "bad arguments");
   if (n_wp < 2) return fail(-1, "fewer than two waypoints");
   if (ni < 1) return fail(-1, "Invalid number of intervals chosen (must be greater than 0)");
@@ -316,6 +317,7 @@ int tcmp_repair_traj(tcmp_handle* h, const double* waypoints, int64_t n_wp, int6
 
 int tcmp_plan_repair(tcmp_handle* h, const tcmp_repair_cfg* cfg, tcmp_repair_result* res) {
   TCMP_ENTER(h);
+  if (int rc = att_refuse(h, "tcmp_plan_repair")) return rc;
   if (!res) return fail(-1, "null result");
   if (!h->plan_open) return fail(-1, "no open plan");
   int max_passes, check_only;

@@ -122,7 +122,14 @@ MAX_GRASP_WIDTH = 0.07                    # panda_primitives.py:194
 GRASP_LENGTH = 0.15                       # panda_primitives.py:195
 TOP_HOLDING_LEFT_ARM = [0, -np.pi / 4, 0.0, -6 * np.pi / 8, 0, np.pi / 2, np.pi / 4]  # utils.py:45
 
-Grasp = namedtuple("Grasp", ["grasp_type", "body", "value", "approach", "carry"])
+class Grasp(namedtuple("Grasp", ["grasp_type", "body", "value", "approach", "carry"])):
+    """utils.py:3351-3365."""
+    __slots__ = ()
+
+    def get_attachment(self, robot, arm):
+        """utils.py:3363-3365: the grasped body on the tool frame at gripper_from_object."""
+        from .utils import PANDA_TOOL_FRAME, Attachment
+        return Attachment(robot, PANDA_TOOL_FRAME, self.value, self.body)
 
 
 def approximate_as_prism(body, body_pose=None):

@@ -89,9 +89,28 @@ class Payload:
         # centre and full extents (w, l, h).  A cylinder's extents are (2r, 2r, h)
         # (vertices_from_data, utils.py:2690-2695); a box passes size=(w, l, h).
         self.center = np.asarray(center, dtype=np.float64).reshape(3)
+        self._cylinder = size is None
         if size is None:
             size = (2 * self.radius, 2 * self.radius, self.height)
         self.size = np.asarray(size, dtype=np.float64).reshape(3)
+
+    def collision_vertices(self, sides=16):
+        """The collision shape's vertices in the body frame, for a held body (utils.Attachment).
+        A box (size given): its 8 corners from center / size.  A cylinder: a regular
+        `sides`-sided prism circumscribed about it (the prism contains the cylinder; its
+        corners lie radius / cos(pi / sides) from the axis, 1.95 % outside at 16 sides) -- an
+        approximation: Bullet's cylinder is exact, and parity with Bullet is not pinned for it,
+        as for every shape here."""
+        half = 0.5 * self.size
+        if not self._cylinder:
+            s = np.array([[sx, sy, sz] for sx in (-1.0, 1.0) for sy in (-1.0, 1.0)
+                          for sz in (-1.0, 1.0)])
+            return self.center + s * half
+        a = 2.0 * np.pi * (np.arange(sides) + 0.5) / sides
+        r = self.radius / np.cos(np.pi / sides)
+        ring = np.stack([r * np.cos(a), r * np.sin(a)], axis=1)
+        return self.center + np.concatenate(
+            [np.column_stack([ring, np.full(sides, z)]) for z in (-half[2], half[2])])
 
     @classmethod
     def coke(cls, mass):

@@ -28,7 +28,7 @@ __all__ = [
     "get_extend_fn", "get_refine_fn", "get_limits_fn", "get_collision_fn", "all_between",
     "convex_combination", "check_initial_end_force_aware", "create_trajectory", "Conf",
     "Trajectory", "get_arm_joints", "get_custom_limits", "get_max_force", "get_max_velocities",
-    "PandaRobot", "Box", "Payload", "get_mass",
+    "PandaRobot", "Box", "Payload", "get_mass", "Attachment",
 ]
 
 
@@ -172,19 +172,75 @@ def get_limits_fn(body, joints, custom_limits={}, verbose=False):  # utils.py:31
     return limits_fn
 
 
+# parent_from_tool of the tool frame (panda_grasptarget_hand xyz 0 0 0.105, panda_mod.urdf:87-91):
+# the tool frame is no collision link, so an attachment on it is placed on panda_hand
+HAND_FROM_TOOL = np.array([[1.0, 0.0, 0.0, 0.0], [0.0, 1.0, 0.0, 0.0], [0.0, 0.0, 1.0, 0.105],
+                           [0.0, 0.0, 0.0, 1.0]])
+
+
+class Attachment(object):
+    """utils.py:3296-3321 Attachment(parent, parent_link, grasp_pose, child): `child` rides on
+    `parent_link` of the robot at parent_from_child = grasp_pose.  parent_link: a collision link's
+    name or its index in COLLISION_LINK_NAMES, or the tool frame PANDA_TOOL_FRAME (folded onto
+    panda_hand with HAND_FROM_TOOL).  grasp_pose: (point, quaternion) or a 4x4 matrix.  child: a
+    Payload (collision_vertices()), a Box or a ConvexMesh, its vertices read in its own pose
+    frame.  The engine tests the child's convex hull against every obstacle at the collision
+    threshold (tcmp_set_attachments)."""
+
+    def __init__(self, parent, parent_link, grasp_pose, child):
+        self.parent = parent
+        self.parent_link = parent_link
+        self.grasp_pose = grasp_pose
+        self.child = child
+
+    def link_and_pose(self):
+        """(collision link index, parent_from_child 4x4) as the engine takes them."""
+        from .ik import to_matrix
+        from .scene import COLLISION_LINK_NAMES
+        gp = self.grasp_pose
+        T = to_matrix(gp) if len(gp) == 2 else np.asarray(gp, dtype=np.float64).reshape(4, 4)
+        link = self.parent_link
+        if isinstance(link, str):
+            if link == PANDA_TOOL_FRAME:
+                return COLLISION_LINK_NAMES.index(PANDA_GRIPPER_ROOT), HAND_FROM_TOOL @ T
+            link = COLLISION_LINK_NAMES.index(link)
+        return int(link), T
+
+    def child_vertices(self):
+        c = self.child
+        if isinstance(c, Payload):
+            return c.collision_vertices()
+        if isinstance(c, ConvexMesh):
+            return c.world_vertices()
+        if isinstance(c, Box):
+            s = np.array([[sx, sy, sz] for sx in (-1.0, 1.0) for sy in (-1.0, 1.0)
+                          for sz in (-1.0, 1.0)])
+            return c.center + (s * c.half_extents) @ c.rotation.T
+        raise TypeError("an attachment's child must be a Payload, a Box or a ConvexMesh")
+
+    def hull(self):
+        from .hull import hull_data
+        return hull_data(self.child_vertices())
+
+    def __repr__(self):
+        return 'a{}'.format(id(self) % 1000)
+
+
 class CollisionFn:
     """get_collision_fn (utils.py:3165-3218): joint limits, the self-collision link pairs when
     self_collisions (get_self_link_pairs, utils.py:3138-3149), then every moving link hull vs
-    every fixed obstacle with the -MAX_DISTANCE closest-point threshold.  Evaluated by the
-    engine (tcmp_check_configs) on a handle of its own, created on first use with the scene
-    uploaded once; rrt_star_force_aware plans on that same handle."""
+    every fixed obstacle with the -MAX_DISTANCE closest-point threshold, then every attachment
+    against every obstacle.  Evaluated by the engine (tcmp_check_configs) on a handle of its own,
+    created on first use with the scene and the attachments uploaded once; rrt_star_force_aware
+    plans on that same handle."""
 
-    def __init__(self, body, obstacles, device=0, self_collisions=False):
+    def __init__(self, body, obstacles, device=0, self_collisions=False, attachments=()):
         self.body = body
         self.obstacles = obstacle_array(obstacles)
         self.meshes = mesh_pack(obstacles)
         self.device = device
         self.self_collisions = bool(self_collisions)
+        self.attachments = list(attachments)
         self._engine = None
 
     @property
@@ -193,6 +249,10 @@ class CollisionFn:
             e = _lib.Engine(self.device)
             e.set_scene(self.obstacles, self.meshes)
             e.set_self_collision(self.self_collisions)
+            if self.attachments:
+                placed = [a.link_and_pose() for a in self.attachments]
+                e.set_attachments([a.hull() for a in self.attachments], [p[0] for p in placed],
+                                  [p[1] for p in placed])
             self._engine = e
         return self._engine
 
@@ -209,14 +269,12 @@ def get_collision_fn(body, joints, obstacles=[], attachments=[], self_collisions
     if disabled_collisions:
         raise NotImplementedError("disabled_collisions are not in the engine (the reference "
                                   "passes set(), panda_primitives.py:270)")
-    if list(attachments):
-        raise NotImplementedError("attachments are not in the engine (the reference planner "
-                                  "passes none, panda_primitives.py:270)")
     if custom_limits:
         raise NotImplementedError("custom joint limits are not in the engine")
     if max_distance != MAX_DISTANCE:
         raise NotImplementedError("the engine's collision threshold is MAX_DISTANCE=0.04")
-    return CollisionFn(body, obstacles, self_collisions=self_collisions)
+    return CollisionFn(body, obstacles, self_collisions=self_collisions,
+                       attachments=list(attachments))
 
 
 def check_initial_end_force_aware(start_conf, end_conf, collision_fn, torque_fn, verbose=True):
