@@ -263,7 +263,9 @@ int tcmp_gauss_clusters(const tcmp_hulls* H, int32_t n, double* records, float* 
 
 /* safe_path_force_aware(extend(from, to), collision, torque) for n edges (rrt_star.py:90-98,
  * utils.py:3068-3077 with the given resolution vector (7, NULL = 0.1 as the planner uses)).
- * n_safe = len(safe prefix), n_steps = len(extend), last = prefix[-1] (valid if n_safe>0). */
+ * n_safe = len(safe prefix), n_steps = len(extend), last = prefix[-1] (valid if n_safe>0).
+ * A resolution that is not finite or not positive: -1 ("resolutions and weights must be
+ * positive"), nothing is launched. */
 int tcmp_check_edges(tcmp_handle* h, const double* from, const double* to, int64_t n,
                      const double* resolutions, int32_t torque_mode, double payload_mass,
                      int32_t* n_safe, int32_t* n_steps, double* last);
@@ -450,7 +452,9 @@ typedef struct {
 } tcmp_plan_result;
 
 /* start a query: checks collision(start), collision(goal) (rrt_star.py:152), allocates the
- * tree and inserts the root.  result->status is set (0 or START_GOAL_COLLISION). */
+ * tree and inserts the root.  result->status is set (0 or START_GOAL_COLLISION).  A weight or
+ * resolution of cfg that is not finite or not positive: -1 ("resolutions and weights must be
+ * positive"), nothing is launched and the handle's state is as before. */
 int tcmp_plan_begin(tcmp_handle* h, const tcmp_plan_cfg* cfg, tcmp_plan_result* result);
 
 /* one round of nb candidates.  samples == NULL: device Philox sampling (batched frontier,
@@ -491,7 +495,8 @@ int tcmp_plan_run_fused(tcmp_handle* const* hs, int32_t n, int64_t n_samples, in
 /* tcmp_plan_begin / tcmp_plan_finish on n engines (cfgs[q], results[q] for hs[q]): every
  * engine's work is queued first, then the host waits once per engine -- a fleet's begins and
  * finishes cost about one device round trip instead of n.  Same results as the one-engine
- * calls; the first failing engine's error is reported (its index in the message). */
+ * calls; the first failing engine's error is reported (its index in the message).  Every cfg's
+ * weights and resolutions are checked as tcmp_plan_begin's before the first engine's launch. */
 int tcmp_plan_begin_many(tcmp_handle* const* hs, int32_t n, const tcmp_plan_cfg* cfgs,
                          tcmp_plan_result* results);
 int tcmp_plan_finish_many(tcmp_handle* const* hs, int32_t n, tcmp_plan_result* results);

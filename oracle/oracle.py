@@ -58,8 +58,8 @@ def lib():
         L.orc_collision.argtypes = [_dp, _dp, ctypes.c_int, ctypes.c_int]
         L.orc_pair_pd.argtypes = [ctypes.c_int, _dp, _dp, ctypes.c_int]
         L.orc_pair_pd.restype = ctypes.c_double
-        L.orc_check_edge.argtypes = [_dp, _dp, _dp, ctypes.c_int, ctypes.c_int, ctypes.c_double,
-                                     ctypes.c_int, _ip, _dp]
+        L.orc_check_edge_res.argtypes = [_dp, _dp, _dp, ctypes.c_int, ctypes.c_int,
+                                         ctypes.c_double, ctypes.c_int, _dp, _ip, _dp]
         L.orc_fk8.argtypes = [_dp, _dp, _dp]
         L.orc_ik8.argtypes = [_dp, _dp, ctypes.c_double, _dp, ctypes.POINTER(ctypes.c_int)]
         L.orc_philox_uniforms.argtypes = [ctypes.c_uint64, ctypes.c_uint64, _dp]
@@ -84,8 +84,9 @@ def lib():
         L.orc_base_pd.argtypes = [_dp, ctypes.c_int, _dp]
         L.orc_body_collision.argtypes = [_dp, _dp, ctypes.c_int, ctypes.c_int]
         L.orc_set_tree_out.argtypes = [_dp, _dp, _ip, ctypes.c_long]
-        L.orc_rrt_run.argtypes = [ctypes.POINTER(RrtCfg), ctypes.POINTER(RrtResult), _dp,
-                                  ctypes.c_long, _dp, _dp, _dp, _dp, ctypes.c_long]
+        L.orc_rrt_run_metric.argtypes = [ctypes.POINTER(RrtCfg), _dp, _dp,
+                                         ctypes.POINTER(RrtResult), _dp, ctypes.c_long, _dp, _dp,
+                                         _dp, _dp, ctypes.c_long]
         assert L.orc_sizeof_cfg() == ctypes.sizeof(RrtCfg), "oracle cfg layout mismatch"
         assert L.orc_sizeof_result() == ctypes.sizeof(RrtResult), "oracle result layout mismatch"
         _lib = L
@@ -278,12 +279,16 @@ def pair_pd_pose_batch(link, fr12, obstacle, method=1, boxes=None):
     return out
 
 
-def check_edge(q1, q2, obs, torque_mode, mass, cull=1):
+def check_edge(q1, q2, obs, torque_mode, mass, cull=1, resolutions=None):
+    """(n_safe, n_steps, last safe configuration) of the edge q1 -> q2; resolutions (7,) are
+    get_extend_fn's (utils.py:3068), None = the planner's 0.1."""
     q1 = _arr(q1, (7,)); q2 = _arr(q2, (7,)); o = obstacles_array(obs)
+    r = None if resolutions is None else _arr(resolutions, (7,))
     ns = ctypes.c_int(0)
     last = np.zeros(7)
-    s = lib().orc_check_edge(_d(q1), _d(q2), _d(o) if len(o) else None, len(o),
-                             int(torque_mode), float(mass), int(cull), ctypes.byref(ns), _d(last))
+    s = lib().orc_check_edge_res(_d(q1), _d(q2), _d(o) if len(o) else None, len(o),
+                                 int(torque_mode), float(mass), int(cull),
+                                 None if r is None else _d(r), ctypes.byref(ns), _d(last))
     return s, ns.value, last
 
 
@@ -329,11 +334,14 @@ def philox_uniforms(seed, k):
 def rrt_run(start, goal, max_samples, obs=None, torque_mode=0, mass=0.0, exec_time=5.0,
             batch=1, seed=0, replay_random=None, replay_uniform=None, radius=0.01,
             goal_prob=0.2, goal_tol=1e-2, cull=1, validate=True, cap_wp=1 << 16,
-            cap_traj=1 << 20, informed=False, threads=1, tree=False):
+            cap_traj=1 << 20, informed=False, threads=1, tree=False, weights=None,
+            resolutions=None):
     """Runs the restated RRT*; returns dict with status, counters, waypoints, traj.
     threads > 1 runs the per-lane loops of a round (nearest, edges, rewire scans) on that
     many OpenMP threads; results do not depend on it (used for bench-size fixtures).
-    tree=True also returns the final tree ("tree_cfg", "tree_cost", "tree_parent")."""
+    tree=True also returns the final tree ("tree_cfg", "tree_cost", "tree_parent").
+    weights / resolutions (7,) are get_distance_fn's and get_extend_fn's; None = the planner's
+    10 and 0.1."""
     cfg = RrtCfg()
     cfg.start[:] = list(map(float, start)); cfg.goal[:] = list(map(float, goal))
     cfg.max_samples = int(max_samples); cfg.batch = int(batch); cfg.torque_mode = int(torque_mode)
@@ -352,6 +360,8 @@ def rrt_run(start, goal, max_samples, obs=None, torque_mode=0, mass=0.0, exec_ti
     if informed and not (replay_uniform is not None and int(batch) == 1):
         raise ValueError("informed is restated for the replayed B = 1 loop only")
     cfg.informed = int(bool(informed))
+    w = None if weights is None else _arr(weights, (7,))
+    r7 = None if resolutions is None else _arr(resolutions, (7,))
     res = RrtResult()
     wp = np.zeros((cap_wp, 7))
     tq = np.zeros((cap_traj, 7)); tqd = np.zeros_like(tq); tqdd = np.zeros_like(tq)
@@ -363,8 +373,9 @@ def rrt_run(start, goal, max_samples, obs=None, torque_mode=0, mass=0.0, exec_ti
         t_par = np.zeros(cap_n, dtype=np.int32)
         lib().orc_set_tree_out(_d(t_cfg), _d(t_cost), t_par.ctypes.data_as(_ip), cap_n)
     try:
-        lib().orc_rrt_run(ctypes.byref(cfg), ctypes.byref(res), _d(wp), cap_wp, _d(tq), _d(tqd),
-                          _d(tqdd), _d(psg), cap_traj)
+        lib().orc_rrt_run_metric(ctypes.byref(cfg), None if w is None else _d(w),
+                                 None if r7 is None else _d(r7), ctypes.byref(res), _d(wp),
+                                 cap_wp, _d(tq), _d(tqd), _d(tqdd), _d(psg), cap_traj)
     finally:
         lib().orc_set_threads(1)
         if tree:

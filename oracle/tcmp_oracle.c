@@ -1187,13 +1187,20 @@ static int orc_edge(orc_ctx* C, const double* q1, const double* q2, int* nsteps,
   return safe;
 }
 
-ORC_API int orc_check_edge(const double* q1, const double* q2, const double* obs, int n_obs,
-                           int torque_mode, double mass, int cull, int* nsteps, double* last) {
+/* res: the 7 edge resolutions of get_extend_fn (utils.py:3068), NULL = the planner's 0.1 */
+ORC_API int orc_check_edge_res(const double* q1, const double* q2, const double* obs, int n_obs,
+                               int torque_mode, double mass, int cull, const double* res,
+                               int* nsteps, double* last) {
   orc_ctx C;
   memset(&C, 0, sizeof(C));
   C.obs = obs; C.n_obs = n_obs; C.torque_mode = torque_mode; C.mass = mass; C.cull = cull;
-  for (int k = 0; k < 7; ++k) { C.res[k] = 0.1; C.w[k] = 10.0; }
+  for (int k = 0; k < 7; ++k) { C.res[k] = res ? res[k] : 0.1; C.w[k] = 10.0; }
   return orc_edge(&C, q1, q2, nsteps, last);
+}
+
+ORC_API int orc_check_edge(const double* q1, const double* q2, const double* obs, int n_obs,
+                           int torque_mode, double mass, int cull, int* nsteps, double* last) {
+  return orc_check_edge_res(q1, q2, obs, n_obs, torque_mode, mass, cull, 0, nsteps, last);
 }
 
 /* ------------------------------------------------------------------------------------ */
@@ -1289,8 +1296,12 @@ static void tree_free(orc_tree* t) {
 
 /* outputs (caller-owned, capacity-checked): waypoints (cap_wp x 7), traj q/qd/qdd
  * (cap_traj x 7), psg (cap_traj) */
-ORC_API int orc_rrt_run(const orc_rrt_cfg* cfg, orc_rrt_result* res, double* wp, long cap_wp,
-                        double* tq, double* tqd, double* tqdd, double* psg, long cap_traj) {
+/* weights, resolutions: get_distance_fn's and get_extend_fn's 7 values each, NULL = the
+ * planner's 10 (1 / radius) and 0.1.  The cfg record and orc_rrt_run keep their layout. */
+ORC_API int orc_rrt_run_metric(const orc_rrt_cfg* cfg, const double* weights,
+                               const double* resolutions, orc_rrt_result* res, double* wp,
+                               long cap_wp, double* tq, double* tqd, double* tqdd, double* psg,
+                               long cap_traj) {
   memset(res, 0, sizeof(*res));
   res->goal_node = -1;
   res->first_fail = -1;
@@ -1298,7 +1309,10 @@ ORC_API int orc_rrt_run(const orc_rrt_cfg* cfg, orc_rrt_result* res, double* wp,
   memset(&C, 0, sizeof(C));
   C.obs = cfg->obs; C.n_obs = cfg->n_obs; C.torque_mode = cfg->torque_mode; C.mass = cfg->mass;
   C.cull = cfg->cull;
-  for (int k = 0; k < 7; ++k) { C.res[k] = 0.1; C.w[k] = 10.0; }
+  for (int k = 0; k < 7; ++k) {
+    C.res[k] = resolutions ? resolutions[k] : 0.1;
+    C.w[k] = weights ? weights[k] : 10.0;
+  }
   /* rrt_star.py:152-154 */
   if (orc_collision(cfg->start, C.obs, C.n_obs, C.cull) || orc_collision(cfg->goal, C.obs, C.n_obs, C.cull)) {
     res->status = 1;
@@ -1490,6 +1504,11 @@ done:
   tree_free(&T);
   free(S); free(dog); free(nn); free(ns); free(nsafe); free(last);
   return res->status;
+}
+
+ORC_API int orc_rrt_run(const orc_rrt_cfg* cfg, orc_rrt_result* res, double* wp, long cap_wp,
+                        double* tq, double* tqd, double* tqdd, double* psg, long cap_traj) {
+  return orc_rrt_run_metric(cfg, 0, 0, res, wp, cap_wp, tq, tqd, tqdd, psg, cap_traj);
 }
 
 /* argmin (rrt_star.py:9-14) of distance(node, s) over nodes [0, T) for each of n samples

@@ -1,7 +1,8 @@
 """Restatement of the best-parent goal connection (include/tcmp.h tcmp_connect_nodes,
 tcmp_plan_connect), the reference of tests/test_connect_host.py and tests/test_gpu_connect.py.
 Nothing here imports the package: the edge check is injected (oracle_check: the CPU oracle's
-check_edge, resolutions 0.1), distances are the distance fn in scalar fp64 in joint order.
+check_edge; its resolutions and the weights w are parameters, left out the planner's 0.1 and
+10), distances are the distance fn in scalar fp64 in joint order.
 
   key       key_i = g_i + dist(c_i, G)
   eligible  key_i < B, strictly (a NaN key fails); B = +inf without a goal node, else its cost
@@ -100,10 +101,10 @@ def connect(cfg, cost, G, check, bound=math.inf, w=W10, tol=1e-2, K=1024, passes
                 node=node, meta=meta)
 
 
-def oracle_check(O, obs, mode, mass):
+def oracle_check(O, obs, mode, mass, resolutions=None):
     """check(a, b) through the CPU oracle's check_edge (Gauss-map exact test, cull=2)."""
     def check(a, b):
-        return O.check_edge(a, b, obs, mode, mass, cull=2)
+        return O.check_edge(a, b, obs, mode, mass, cull=2, resolutions=resolutions)
     return check
 
 

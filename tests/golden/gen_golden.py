@@ -20,6 +20,8 @@ Outputs (small npz fixtures, no pickles) in tests/golden/:
                        FK the IK round trip is checked with (ikfast itself is unbuildable here)
   rrt_<name>.npz       full reference RRT* runs: RNG streams consumed, waypoints,
                        trajectory q/qd/qdd/psg (strided subsample for long ones)
+  rrtw_<name>.npz      the same under other distance weights / edge resolutions than the
+                       planner's 10 / 0.1 (--only-weighted); both vectors are stored
 """
 import os
 import random
@@ -56,9 +58,11 @@ def difference_fn(q2, q1):               # utils.py:2995-3001 (no circular joint
     return tuple(v2 - v1 for v2, v1 in zip(q2, q1))
 
 
-def distance_fn(q1, q2):                 # utils.py:3010-3017
-    diff = np.array(difference_fn(q2, q1))
-    return np.sqrt(np.dot(WEIGHTS, diff * diff))
+def make_distance_fn(weights):           # utils.py:3010-3017
+    def distance_fn(q1, q2):
+        diff = np.array(difference_fn(q2, q1))
+        return np.sqrt(np.dot(weights, diff * diff))
+    return distance_fn
 
 
 def refine_fn(q1, q2, num_steps):        # utils.py:3031-3041
@@ -70,9 +74,11 @@ def refine_fn(q1, q2, num_steps):        # utils.py:3031-3041
         yield q
 
 
-def extend_fn(q1, q2):                   # utils.py:3068-3077
-    steps = int(np.linalg.norm(np.divide(difference_fn(q2, q1), RADIUS), ord=2))
-    return refine_fn(q1, q2, steps)
+def make_extend_fn(resolutions):         # utils.py:3068-3077
+    def extend_fn(q1, q2):
+        steps = int(np.linalg.norm(np.divide(difference_fn(q2, q1), resolutions), ord=2))
+        return refine_fn(q1, q2, steps)
+    return extend_fn
 
 
 def all_between(lo, v, hi):              # utils.py:1150-1154
@@ -286,7 +292,13 @@ class _NodeLog:
 
 
 def run_reference(name, start, goal, obs, mode, mass, exec_time, iters, seed, stride=1,
-                  want_found=None, informed=False, radius=0.01):
+                  want_found=None, informed=False, radius=0.01, weights=None, resolutions=None):
+    """weights / resolutions None: the planner's WEIGHTS / RADIUS, written as rrt_<name>.npz;
+    given: both are stored and the file is rrtw_<name>.npz."""
+    weighted = weights is not None or resolutions is not None
+    weights = WEIGHTS if weights is None else np.asarray(weights, dtype=np.float64)
+    resolutions = RADIUS if resolutions is None else np.asarray(resolutions, dtype=np.float64)
+    distance_fn, extend_fn = make_distance_fn(weights), make_extend_fn(resolutions)
     problem = Problem(mass, exec_time, mode)
     torque_fn = TESTS[mode](problem)
     collision_fn = make_collision_fn(obs)
@@ -322,6 +334,8 @@ def run_reference(name, start, goal, obs, mode, mass, exec_time, iters, seed, st
                n_rewires=np.array(log.rewires))
     cfg, cost, par = log.arrays()
     res["tree_cfg"], res["tree_cost"], res["tree_parent"] = cfg, cost, par
+    if weighted:
+        res["weights"], res["resolutions"] = weights, resolutions
     if wp_rec:
         res["waypoints"] = wp_rec[-1]
     if path is not None:
@@ -331,7 +345,8 @@ def run_reference(name, start, goal, obs, mode, mass, exec_time, iters, seed, st
         res["traj_idx"] = idx
         res["q"] = q[idx]; res["qd"] = qd[idx]; res["qdd"] = qdd[idx]; res["psg"] = p[idx]
         res["sum_q"] = q.sum(0); res["sum_qd"] = qd.sum(0); res["sum_qdd"] = qdd.sum(0)
-    np.savez_compressed(os.path.join(HERE, "rrt_%s.npz" % name), **res)
+    np.savez_compressed(os.path.join(HERE, "%s_%s.npz" % ("rrtw" if weighted else "rrt", name)),
+                        **res)
     print("%-22s found=%s waypoints=%s traj=%s random=%d uniform=%d nodes=%d rewires=%d  %.1fs" % (
         name, path is not None, len(wp_rec[-1]) if wp_rec else None,
         len(path) if path is not None else None, len(rnd.vals), len(sample.u), len(cfg),
@@ -422,7 +437,52 @@ def gen_rewire():
             raise RuntimeError("no rewiring golden query for " + name)
 
 
+W_NONUNI = np.array([10.0, 3.0, 7.5, 1.0, 20.0, 0.5, 10.0])
+R_NONUNI = np.array([0.05, 0.1, 0.2, 0.1, 0.4, 0.3, 0.125])
+DEFAULT_RESOLUTION = np.radians(3)       # utils.py:3061
+
+
+def gen_weighted():
+    """Reference runs under distance weights and edge resolutions other than the planner's
+    10 / 0.1 (every other golden): per-joint vectors, the drop-in API's own defaults
+    (get_distance_fn weights ones, get_extend_fn DEFAULT_RESOLUTION; utils.py:3003-3008,
+    3061-3066), and non-uniform weights at the planner's radius, where nothing rewires.  The
+    first two reuse the query of rrt_empty_rne5.npz; the others search for one that reaches the
+    goal (pick_query's pre-screen runs the oracle at its defaults: it only picks queries)."""
+    z = np.load(os.path.join(HERE, "rrt_empty_rne5.npz"))
+    ones = np.ones(7)
+    fixed = [  # name, weights, resolutions, radius, iterations, min rewires
+        ("nonuni_rewire", W_NONUNI, R_NONUNI, 6.0, 300, 20),
+        ("defaults_api", ones, DEFAULT_RESOLUTION * ones, 2.0, 200, 1),
+    ]
+    for name, w, r, radius, iters, min_rw in fixed:
+        run_reference(name, z["start"], z["goal"], [], "rne", 5.0, 1.0, iters, 11, stride=7,
+                      radius=radius, weights=w, resolutions=r)
+        if int(np.load(os.path.join(HERE, "rrtw_%s.npz" % name))["n_rewires"]) < min_rw:
+            raise RuntimeError("too few rewires in " + name)
+    rng = np.random.default_rng(8765)
+    searched = [  # name, obstacles, mode, mass, weights, resolutions, radius, iterations, seed
+        ("nonuni_box8", 8, "nov", 2.0, W_NONUNI, R_NONUNI, 4.0, 200, 21),
+        ("decoupled_r001", 4, "base", 0.0, W_NONUNI, 0.1 * ones, 0.01, 200, 22),
+    ]
+    for name, n_obs, mode, mass, w, r, radius, iters, seed in searched:
+        for attempt in range(60):
+            s, g, o = pick_query(rng, n_obs, mode, mass, need_block=True, iters=iters)
+            if not run_reference(name, s, g, o, mode, mass, 5.0, iters, seed + 100 * attempt,
+                                 stride=37, want_found=True, radius=radius, weights=w,
+                                 resolutions=r):
+                continue
+            n_rw = int(np.load(os.path.join(HERE, "rrtw_%s.npz" % name))["n_rewires"])
+            if (n_rw == 0) if radius == 0.01 else (n_rw >= 1):
+                break
+        else:
+            raise RuntimeError("no weighted golden query for " + name)
+
+
 def main():
+    if "--only-weighted" in sys.argv:
+        gen_weighted()
+        return
     if "--only-rewire" in sys.argv:
         gen_rewire()
         return

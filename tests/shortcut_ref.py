@@ -1,8 +1,9 @@
 """Restatement of the force-aware shortcut pass (include/tcmp.h tcmp_shortcut_path), the
 reference of tests/test_shortcut_host.py and tests/test_gpu_shortcut.py.  Nothing here imports
-the package: chord checks come from the CPU oracle (oracle.check_edge, resolutions 0.1 and
-weights 10, the planner's defaults), distances are orc_dist restated in scalar fp64 in its loop
-order, the dynamic program and the splice are plain loops.
+the package: chord checks come from the CPU oracle (oracle.check_edge), distances are orc_dist
+restated in scalar fp64 in its loop order, the dynamic program and the splice are plain loops.
+The extend resolutions and the distance weights w are parameters; left out they are the
+planner's 0.1 and 10.
 
 One pass over W[0..n-1]:
   anchors  a_k = min(k s, n - 1), s = 1 if n <= A_max else ceil((n - 1) / (A_max - 1)),
@@ -90,7 +91,7 @@ def splice(W, anc, hop_list, n_steps_of):
     return np.array(new).reshape(-1, 7)
 
 
-def one_pass(W, check, a_max):
+def one_pass(W, check, a_max, w=W10):
     """check(a, b) -> (n_safe, n_steps, last).  -> (new list, stats of the pass)."""
     W = np.asarray(W, dtype=np.float64).reshape(-1, 7)
     n = len(W)
@@ -100,7 +101,7 @@ def one_pass(W, check, a_max):
     for k in range(A - 1):
         acc = 0.0
         for t in range(anc[k], anc[k + 1]):
-            acc = acc + dist(W[t], W[t + 1])
+            acc = acc + dist(W[t], W[t + 1], w)
         orig.append(acc)
     valid, n_steps_of = {}, {}
     tested = steps = 0
@@ -111,8 +112,8 @@ def one_pass(W, check, a_max):
             tested += 1
             ns, nt, last = check(W[anc[k]], W[anc[l]])
             steps += nt if ns == nt else ns + 1
-            if ns == nt and dist(W[anc[l]], last) < 1e-6:
-                valid[(k, l)] = dist(W[anc[k]], W[anc[l]])
+            if ns == nt and dist(W[anc[l]], last, w) < 1e-6:
+                valid[(k, l)] = dist(W[anc[k]], W[anc[l]], w)
                 n_steps_of[(k, l)] = nt
     cost, pred = dp(orig, valid)
     hl = hops(pred)
@@ -125,12 +126,12 @@ def one_pass(W, check, a_max):
                      cost_before=before, cost_after=cost[A - 1])
 
 
-def shortcut(W, check, a_max=512, passes=1):
+def shortcut(W, check, a_max=512, passes=1, w=W10):
     W = np.asarray(W, dtype=np.float64).reshape(-1, 7)
     tot = dict(passes_run=0, n_before=len(W), chords_tested=0, chords_valid=0, chords_used=0,
                chord_steps=0, max_hops=0)
     for p in range(passes):
-        W, st = one_pass(W, check, a_max)
+        W, st = one_pass(W, check, a_max, w)
         if p == 0:
             tot["n_anchors"] = st["n_anchors"]
             tot["cost_before"] = st["cost_before"]
@@ -147,21 +148,22 @@ def shortcut(W, check, a_max=512, passes=1):
     return W, tot
 
 
-def oracle_check(O, obs, mode, mass):
+def oracle_check(O, obs, mode, mass, resolutions=None):
     """check(a, b) through the CPU oracle's check_edge (Gauss-map exact test, cull=2)."""
     def check(a, b):
-        return O.check_edge(a, b, obs, mode, mass, cull=2)
+        return O.check_edge(a, b, obs, mode, mass, cull=2, resolutions=resolutions)
     return check
 
 
-def path_cost(W):
+def path_cost(W, w=W10):
     c = 0.0
     for t in range(len(W) - 1):
-        c = c + dist(W[t], W[t + 1])
+        c = c + dist(W[t], W[t + 1], w)
     return c
 
 
-def zigzag(O, rng, n, obs, mode, mass, lo, hi, step=0.9, verts=False, free=False):
+def zigzag(O, rng, n, obs, mode, mass, lo, hi, step=0.9, verts=False, free=False,
+           resolutions=None):
     """A polyline of n points: zig-zag vertices at most `step` apart per joint, joined by the
     extend rule's points (verts: the vertices alone).  Every vertex is collision-free and within
     the torque limits and every hop's edge is safe, so the original hops are valid edges --
@@ -176,7 +178,7 @@ def zigzag(O, rng, n, obs, mode, mass, lo, hi, step=0.9, verts=False, free=False
     while len(pts) < n:
         for _ in range(2000):
             nv = np.clip(v + rng.uniform(-step, step, 7), lo, hi)
-            ns, nt, _ = O.check_edge(v, nv, obs, mode, mass, cull=2)
+            ns, nt, _ = O.check_edge(v, nv, obs, mode, mass, cull=2, resolutions=resolutions)
             if free or ns == nt:
                 break
         else:

@@ -114,3 +114,35 @@ def test_python_surface():
     assert (p["connect_candidates"].default, p["connect_passes"].default) == (1024, 1)
     p = inspect.signature(_lib.Engine.plan_connect).parameters
     assert (p["max_candidates"].default, p["passes"].default) == (1024, 1)
+
+
+def test_restatement_under_other_weights_and_resolutions():
+    """The restatement with per-joint weights and resolutions (tests/metric_cases.py): keys and
+    costs in the weighted distance, verdicts through oracle.check_edge(resolutions=) equal to the
+    plain Python walk of the reference's extend."""
+    import metric_cases as MC
+    q, W, cost, refs = MC.connect_case(O)
+    r = refs[(32, 8)]["result"]
+    print(r)
+    assert r["status"] == CR.OK and r["passes_run"] >= 2 and r["n_tested"] < r["n_selected"], \
+        (r, "the fixture proves nothing")
+    assert 0 < r["n_valid"] < r["n_tested"] and (refs[(32, 8)]["nsafe"] == -1).any()
+    assert refs[(300, 1)]["result"]["n_tested"] == 300
+    key = np.array([cost[i] + CR.distance(W[i], q["goal"], MC.W_NONUNI) for i in range(len(W))])
+    assert key.tobytes() == CR.keys(W, cost, q["goal"], MC.W_NONUNI).tobytes()
+    assert key.tobytes() != CR.keys(W, cost, q["goal"]).tobytes()
+    py = MC.ref_check(O, q["obs"], CR.MODE, CR.MASS, MC.R_NONUNI)
+    for (K, p), ref in refs.items():
+        o = CR.connect(W, cost, q["goal"], py, w=MC.W_NONUNI, K=K, passes=p)
+        assert o["result"] == ref["result"]
+        for k in ("ids", "keys", "nsafe", "nsteps", "node"):
+            assert o[k].tobytes() == ref[k].tobytes(), k
+        rr = ref["result"]
+        i, last = rr["parent"], ref["node"][:7]
+        assert rr["cost_after"] == cost[i] + CR.distance(W[i], last, MC.W_NONUNI)
+        assert CR.distance(last, q["goal"], MC.W_NONUNI) < 1e-2
+    # the planner's resolutions give other step counts for the same candidates
+    at01 = CR.connect(W, cost, q["goal"], CR.oracle_check(O, q["obs"], CR.MODE, CR.MASS),
+                      w=MC.W_NONUNI, K=300, passes=1)
+    assert at01["ids"].tobytes() == refs[(300, 1)]["ids"].tobytes()
+    assert at01["nsteps"].tobytes() != refs[(300, 1)]["nsteps"].tobytes()

@@ -9,6 +9,7 @@ import pytest
 from conftest import GOLDEN
 
 import oracle as O
+import metric_cases as MC
 
 LO = np.array([-2.8973, -1.7628, -2.8973, -3.0718, -2.8973, -0.0175, -2.8973])
 HI = np.array([2.8973, 1.7628, 2.8973, -0.0698, 2.8973, 3.7525, 2.8973])
@@ -38,19 +39,17 @@ def test_minjerk_zero_intervals_asserts():
 
 
 RRT = sorted(glob.glob(os.path.join(GOLDEN, "rrt_*.npz")))
+RRTW = sorted(glob.glob(os.path.join(GOLDEN, "rrtw_*.npz")))
 
 
-@pytest.mark.parametrize("path", RRT, ids=[os.path.basename(p) for p in RRT])
-def test_rrt_replay_matches_reference(path):
-    """Oracle RRT* (B=1) fed the RNG streams the reference consumed reproduces its output."""
-    z = np.load(path)
+def _replay_matches(z, **metric):
     rr = z["replay_random"] if len(z["replay_random"]) else np.zeros(0)
     ru = z["replay_uniform"] if len(z["replay_uniform"]) else np.zeros((0, 7))
     radius = float(z["radius"]) if "radius" in z else 0.01
     r = O.rrt_run(z["start"], z["goal"], int(z["iters"]), z["obs"], int(z["mode"]),
                   float(z["mass"]), float(z["exec_time"]), replay_random=rr, replay_uniform=ru,
                   informed=bool(z["informed"]) if "informed" in z else False, radius=radius,
-                  tree="tree_cfg" in z)
+                  tree="tree_cfg" in z, **metric)
     if "tree_cfg" in z:
         # the reference's OptimalNode graph, node by node, and its rewire count
         assert r["n_rewires"] == int(z["n_rewires"])
@@ -71,6 +70,95 @@ def test_rrt_replay_matches_reference(path):
     assert np.abs(r["qdd"][idx] - z["qdd"]).max() < 1e-12
     assert np.abs(r["psg"][idx] - z["psg"]).max() < 1e-15
     assert np.abs(r["q"].sum(0) - z["sum_q"]).max() < 1e-9
+
+
+@pytest.mark.parametrize("path", RRT, ids=[os.path.basename(p) for p in RRT])
+def test_rrt_replay_matches_reference(path):
+    """Oracle RRT* (B=1) fed the RNG streams the reference consumed reproduces its output."""
+    _replay_matches(np.load(path))
+
+
+# name: (weights, resolutions, radius, must be found, rewires at least, rewires at most)
+WEIGHTED = {
+    "nonuni_rewire": (MC.W_NONUNI, MC.R_NONUNI, 6.0, None, 20, None),
+    "nonuni_box8": (MC.W_NONUNI, MC.R_NONUNI, 4.0, True, 1, None),
+    "defaults_api": (MC.ONES, MC.DEFAULT_RESOLUTION * MC.ONES, 2.0, None, 1, None),
+    "decoupled_r001": (MC.W_NONUNI, 0.1 * MC.ONES, 0.01, True, 0, 0),
+}
+
+
+def test_weighted_fixtures_are_the_four():
+    """The reference runs under other weights and resolutions than the planner's 10 / 0.1 (gen_
+    golden.py --only-weighted): the vectors and radii they were asked for, the rewire counts that
+    make them worth replaying, and at least two trajectories."""
+    assert [os.path.basename(p)[5:-4] for p in RRTW] == sorted(WEIGHTED)
+    found = 0
+    for p in RRTW:
+        z = np.load(p)
+        w, res, radius, must_find, rw_min, rw_max = WEIGHTED[os.path.basename(p)[5:-4]]
+        assert np.array_equal(z["weights"], w) and np.array_equal(z["resolutions"], res)
+        assert float(z["radius"]) == radius and int(z["iters"]) <= 300
+        assert int(z["n_rewires"]) >= rw_min
+        assert rw_max is None or int(z["n_rewires"]) <= rw_max
+        assert must_find is None or bool(z["found"]) == must_find
+        assert os.path.getsize(p) < 100_000
+        found += bool(z["found"])
+    assert found >= 2
+
+
+@pytest.mark.parametrize("path", RRTW, ids=[os.path.basename(p) for p in RRTW])
+def test_rrt_weighted_replay_matches_reference(path):
+    """The same replay with the fixture's own distance weights, edge resolutions and radius."""
+    z = np.load(path)
+    _replay_matches(z, weights=z["weights"], resolutions=z["resolutions"])
+
+
+def test_weighted_fixtures_need_their_metric():
+    """The replay at the oracle's defaults does not reproduce them: the parameters matter."""
+    for p in RRTW:
+        z = np.load(p)
+        with pytest.raises(AssertionError):
+            _replay_matches(z)
+
+
+@pytest.mark.parametrize("name", list(MC.RESOLUTIONS) + ["default_resolution"])
+def test_check_edge_resolutions_vs_restatement(name):
+    """oracle.check_edge(resolutions=) == the plain restatement of get_extend_fn / get_refine_fn
+    (utils.py:3031-3077) under safe_path_force_aware (rrt_star.py:90-98), on 200 random edges in
+    eight boxes under the rne test at 5 kg: step counts, safe prefix and last point bit for bit."""
+    res = MC.RESOLUTIONS.get(name, MC.DEFAULT_RESOLUTION * MC.ONES)
+    obs = MC.box_scene(8, 8)
+    a, b = MC.random_edges(np.random.default_rng(len(name)), 200)
+    cut = 0
+    for x, y in zip(a, b):
+        s, n, last = O.check_edge(x, y, obs, MC.MODE_RNE, 5.0, cull=2, resolutions=res)
+        rs, rn, rlast = MC.check_edge_ref(O, x, y, obs, MC.MODE_RNE, 5.0, res)
+        assert (s, n) == (rs, rn)
+        if s:
+            assert last.tobytes() == rlast.tobytes()
+        cut += 0 < s < n
+    assert cut >= 10  # prefixes that end inside an edge are among them
+    if name == "uni1":
+        assert {O.check_edge(x, y, obs, 0, 0.0, resolutions=res)[1] for x, y in zip(a, b)} \
+            >= set(range(1, 8))
+
+
+def test_check_edge_resolutions_none_is_the_planners():
+    a, b = MC.random_edges(np.random.default_rng(5), 50)
+    for x, y in zip(a, b):
+        s, n, last = O.check_edge(x, y, MC.NO_OBS, MC.MODE_RNE, 5.0)
+        s2, n2, last2 = O.check_edge(x, y, MC.NO_OBS, MC.MODE_RNE, 5.0, resolutions=[0.1] * 7)
+        assert (s, n, last.tobytes()) == (s2, n2, last2.tobytes())
+
+
+def test_check_edge_hand_built():
+    """An edge of no length is one step; an edge whose scaled norm is exactly 3 takes 4."""
+    for x, y, res, steps in MC.hand_edges():
+        s, n, last = O.check_edge(x, y, MC.NO_OBS, MC.MODE_BASE, 0.0, cull=2, resolutions=res)
+        assert (s, n) == (steps, steps) and last.tobytes() == y.tobytes()
+        assert MC.check_edge_ref(O, x, y, MC.NO_OBS, MC.MODE_BASE, 0.0, res)[:2] == (steps, steps)
+        # one joint decides the count: the other joints' resolutions do not enter
+        assert len(MC.extend_ref(x, y, res)) == steps
 
 
 def test_collision_bounds_are_exact():

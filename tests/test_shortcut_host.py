@@ -208,3 +208,30 @@ def test_no_gpu_means_loud_failure():
         return  # a GPU is visible: tests/test_gpu_shortcut.py covers the calls
     with pytest.raises(_lib.TcmpError):
         _lib.Engine(0).shortcut_path(np.zeros((3, 7)), 2, 5.0)
+
+
+def test_restatement_under_other_weights_and_resolutions():
+    """The restatement with per-joint weights and resolutions (tests/metric_cases.py): chord
+    checks through oracle.check_edge(resolutions=) give what the plain Python walk of the
+    reference's extend gives, the dynamic program minimises the weighted length, and neither
+    vector is the planner's in disguise."""
+    import metric_cases as MC
+    c = MC.shortcut_case(O)
+    W, ref, st = c["W"], c["ref"], c["st"]
+    print(st)
+    assert st["chords_used"] >= 2 and st["max_hops"] > st["chords_used"], "the fixture proves nothing"
+    assert st["chords_tested"] - st["chords_valid"] >= 1
+    assert ref[0].tobytes() == W[0].tobytes() and ref[-1].tobytes() == W[-1].tobytes()
+    assert st["cost_before"] == SR.path_cost(W, MC.W_NONUNI) != SR.path_cost(W)
+    assert abs(st["cost_after"] - SR.path_cost(ref, MC.W_NONUNI)) <= 1e-12 * st["cost_after"]
+    assert st["cost_after"] < st["cost_before"]
+    # the oracle's edges with resolutions against the plain restatement of utils.py:3031-3077
+    py, st_py = SR.shortcut(W, MC.ref_check(O, c["obs"], c["mode"], c["mass"], MC.R_NONUNI),
+                            512, 1, MC.W_NONUNI)
+    assert py.tobytes() == ref.tobytes() and st_py == st
+    # each vector alone changes the answer
+    check10 = SR.oracle_check(O, c["obs"], c["mode"], c["mass"])
+    only_w, st_w = SR.shortcut(W, check10, 512, 1, MC.W_NONUNI)
+    only_r, st_r = SR.shortcut(W, SR.oracle_check(O, c["obs"], c["mode"], c["mass"], MC.R_NONUNI))
+    assert st_w["chord_steps"] != st["chord_steps"] == st_r["chord_steps"]
+    assert st_r["cost_before"] != st["cost_before"] == st_w["cost_before"]

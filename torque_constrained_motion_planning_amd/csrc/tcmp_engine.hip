@@ -48,6 +48,15 @@ int fail(int code, const std::string& msg) {
   return code;
 }
 
+// A zero, negative or NaN resolution makes every edge num_steps' 1,048,577-step cap, and such a
+// weight makes distance() NaN: refused before anything is launched (v: 7 values, or null).
+bool metric_ok(const double* v) {
+  for (int k = 0; v && k < 7; ++k)
+    if (!(v[k] > 0.0) || !std::isfinite(v[k])) return false;
+  return true;
+}
+const char* const kBadMetric = "resolutions and weights must be positive";
+
 // Process-wide dispatch lock.  Every C-ABI entry point that touches a device holds it shared
 // (reentrant per thread: nested entries take it once); a round-graph capture (tcmp_plan_run)
 // holds it exclusively from hipStreamBeginCapture through the graph's instantiation and first
@@ -3403,6 +3412,7 @@ int tcmp_check_edges(tcmp_handle* h, const double* from, const double* to, int64
   if (n < 0 || n > INT_MAX || (n > 0 && (!from || !to || !n_safe || !n_steps || !last)))
     return fail(-1, "bad arguments");
   if (torque_mode < 0 || torque_mode > 3) return fail(-1, "unknown torque mode");
+  if (!metric_ok(resolutions)) return fail(-1, kBadMetric);
   if (n == 0) return 0;
   int rc = upload7(h, h->s0, from, n);
   rc = rc ? rc : upload7(h, h->s1, to, n);
@@ -3569,6 +3579,7 @@ __global__ void k_plan_init(const tcmp_handle::Pin* b, double* cfg, double* tgt,
 int plan_begin_launch(tcmp_handle* h, const tcmp_plan_cfg* cfg, tcmp_plan_result* result) {
   if (!cfg || !result) return fail(-1, "null cfg/result");
   if (cfg->torque_mode < 0 || cfg->torque_mode > 3) return fail(-1, "unknown torque mode");
+  if (!metric_ok(cfg->resolutions) || !metric_ok(cfg->weights)) return fail(-1, kBadMetric);
   if (cfg->max_nodes < 2 || cfg->max_batch < 1) return fail(-1, "bad capacities");
   memset(result, 0, sizeof(*result));
   result->goal_node = -1;
@@ -3710,6 +3721,9 @@ int tcmp_plan_begin_many(tcmp_handle* const* hs, int32_t n, const tcmp_plan_cfg*
   if (!hs || n < 1 || !cfgs || !results) return fail(-1, "bad arguments");
   for (int q = 0; q < n; ++q)
     if (int rc = att_refuse(hs[q], "tcmp_plan_begin_many")) return rc;
+  for (int q = 0; q < n; ++q)  // before the first engine's launch
+    if (!metric_ok(cfgs[q].resolutions) || !metric_ok(cfgs[q].weights))
+      return fail(-1, "plan " + std::to_string(q) + ": " + kBadMetric);
   for (int q = 0; q < n; ++q) {
     int rc = set_dev(hs[q]);
     rc = rc ? rc : plan_begin_launch(hs[q], cfgs + q, results + q);
