@@ -94,7 +94,7 @@ void k_goal_torque(double* __restrict__ sols, const int* __restrict__ count, int
       hr = INFINITY;
 #pragma unroll
       for (int j = 0; j < 6; ++j) {
-        tok &= !(fabs(t[j]) >= kEffort[j]);  // torque_ok's comparison: a NaN fails
+        tok &= !(fabs(t[j]) >= kEffort[j]);  // torque_ok's comparison: a NaN passes
         hr = fmin(hr, (kEffort[j] - fabs(t[j])) / kEffort[j]);
       }
     }
