@@ -365,6 +365,52 @@ int tcmp_connect_nodes(tcmp_handle* h, const double* nodes, const double* cost, 
                        double* keys_out, int32_t* nsafe_out, int32_t* nsteps_out, int64_t cap_out,
                        double* node_out, tcmp_connect_result* res);
 
+/* Goal-set connection: the stage above with one change -- each node is tried toward the goal of
+ * a given set that is nearest to it.  A grasp pose has a whole family of goal configurations
+ * (joint 7 is free, up to 8 IK branches per value; tcmp_goal_search lists the feasible ones);
+ * the rounds and tcmp_plan_connect aim at one.  Opt-in; nothing else changes.
+ *
+ * Inputs: the nodes (c_i, g_i), i = 0 .. T-1, goals G_0 .. G_{n-1} with 1 <= n <= 256, the
+ * weights w and the bound B as for tcmp_connect_nodes.
+ *   nearest   s_ij = sum_k w_k * (d * d) with d = G_jk - c_ik, k ascending, fp64, no contraction:
+ *             the distance fn's sum before its square root.  j*(i) is the lowest j attaining
+ *             min_j s_ij (a strict < scanning j ascending); a NaN s_ij never wins.  The rule is
+ *             on s, not on the distance: a square root that maps two sums to one value cannot
+ *             change j*.  Duplicate goals are allowed; the lowest index wins
+ *   key       key_i = g_i + sqrt(s_{i j*}) = g_i + min_j distance(c_i, G_j, w) (sqrt is
+ *             monotone); with n = 1 it is tcmp_connect_nodes' key bit for bit
+ *   eligible, selected, pass, outcome: as tcmp_connect_nodes words them with G replaced per
+ *             candidate by G_{j*(i)}: the edge tested is c_i -> G_{j*(i)}; the candidate is valid
+ *             iff n_safe > 0 and distance(last, G_{j*(i)}, w) < goal_tolerance;
+ *             c = g_i + distance(c_i, last, w); the winner is the valid candidate with c < B
+ *             smallest by (c, rank); the first pass with a winner ends the stage.  B is the
+ *             current goal node's cost, whichever goal it reached
+ * Beyond tcmp_connect_result: goal_index of the winner (TREE_FULL too; -1: none), and per goal
+ * three counts -- near (eligible nodes whose j* is that goal), tested and valid (over the passes
+ * run): which of the goals the tree can reach.
+ * A node is tried toward its nearest goal only: on a one-node tree exactly one goal is tried, and
+ * a blocked goal shadows the others for the nodes nearest to it.  The counts show it (tested > 0,
+ * valid == 0); the answer is a second call without that goal.  (Pairs (i, j) as candidates would
+ * need T x n keys: this is why the rule is per node.)
+ * Refused with -1 and nothing launched: n_goals outside 1..256, a goal value that is not finite,
+ * and what tcmp_connect_nodes refuses.  Goals outside the joint limits, in collision or over the
+ * torque limits are not refused: their edges fail. */
+typedef struct {
+  tcmp_connect_result r;
+  int32_t n_goals, goal_index;
+} tcmp_connect_set_result;
+
+/* the stand-alone form: tcmp_connect_nodes' arguments with goals (n_goals x 7) for the goal.
+ * goal_out (cap_out, counted in the -4 rule): j* of the selected ranks, -1 for ranks never tested,
+ * as nsafe_out.  per_goal (3 x n_goals: the near, the tested, the valid counts; may be NULL). */
+int tcmp_connect_goal_set(tcmp_handle* h, const double* nodes, const double* cost, int64_t n_nodes,
+                          const double* goals, int32_t n_goals, double bound,
+                          const double* resolutions, const double* weights, double goal_tolerance,
+                          int32_t torque_mode, double payload_mass, const tcmp_connect_cfg* cfg,
+                          int32_t* ids_out, double* keys_out, int32_t* goal_out,
+                          int32_t* nsafe_out, int32_t* nsteps_out, int64_t cap_out,
+                          double* node_out, int64_t* per_goal, tcmp_connect_set_result* res);
+
 /* argmin over tree nodes of the weighted distance (rrt_star.py:9-14,171), first index wins
  * ties.  tree: T x 7, samples: n x 7, weights: 7 positive (NULL = 10 = 1/radius).  Runs the
  * planner's own nearest path: the radix-tree cell index of the tree and the pruned exact
@@ -539,6 +585,17 @@ int tcmp_plan_shortcut(tcmp_handle* h, const tcmp_shortcut_cfg* cfg, tcmp_shortc
  * tcmp_plan_run_fused; the ranks of a shared tree must each call it (determinism keeps them
  * equal). */
 int tcmp_plan_connect(tcmp_handle* h, const tcmp_connect_cfg* cfg, tcmp_connect_result* res);
+
+/* tcmp_connect_goal_set's stage on the open plan's tree, with the plan's weights, resolutions,
+ * goal tolerance, torque mode and payload mass, in tcmp_plan_connect's place and with its
+ * effects: on OK one node is appended whose extend target is G_{j*}, the goal actually aimed at
+ * (so the retrace regenerates the edge), and it becomes the goal node; NONE and TREE_FULL leave
+ * every byte as it was.  The plan's own goal is not added to the set: the caller lists it if it
+ * wants it.  A tree rooted at the start can so be connected to a new goal set without planning
+ * again.  per_goal: 3 x n_goals, may be NULL. */
+int tcmp_plan_connect_goal_set(tcmp_handle* h, const double* goals, int32_t n_goals,
+                               const tcmp_connect_cfg* cfg, int64_t* per_goal,
+                               tcmp_connect_set_result* res);
 
 /* Torque-feasible retiming (no reference counterpart: the reference returns nothing when one
  * row of the trajectory fails the final torque test, rrt_star.py:208-210).  Playing the same rows

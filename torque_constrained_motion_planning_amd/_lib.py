@@ -39,6 +39,7 @@ EXPORTS = [
     "tcmp_gather_layout", "tcmp_gather_pack", "tcmp_gather_unpack", "tcmp_dist_rccl_ranks",
     "tcmp_shortcut_path", "tcmp_plan_shortcut",
     "tcmp_connect_nodes", "tcmp_plan_connect",
+    "tcmp_connect_goal_set", "tcmp_plan_connect_goal_set",
     "tcmp_retime_traj", "tcmp_plan_retime",
     "tcmp_repair_traj", "tcmp_plan_repair",
     "tcmp_minjerk_runs", "tcmp_retime_runs_traj", "tcmp_plan_retime_runs",
@@ -148,6 +149,15 @@ class ConnectResult(ctypes.Structure):
 
     def as_dict(self):
         return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+class ConnectSetResult(ctypes.Structure):
+    """tcmp_connect_set_result"""
+    _fields_ = [("r", ConnectResult), ("n_goals", ctypes.c_int32),
+                ("goal_index", ctypes.c_int32)]
+
+    def as_dict(self):
+        return dict(self.r.as_dict(), n_goals=self.n_goals, goal_index=self.goal_index)
 
 
 class RetimeCfg(ctypes.Structure):
@@ -360,6 +370,15 @@ def load_library(path=LIB_PATH):
                                              ctypes.POINTER(ConnectResult)]
             L.tcmp_plan_connect.argtypes = [vp, ctypes.POINTER(ConnectCfg),
                                             ctypes.POINTER(ConnectResult)]
+        if hasattr(L, "tcmp_connect_goal_set"):  # absent from A/B builds of older sources
+            L.tcmp_connect_goal_set.argtypes = [
+                vp, _dp, _dp, ctypes.c_int64, _dp, ctypes.c_int32, ctypes.c_double, _dp, _dp,
+                ctypes.c_double, ctypes.c_int32, ctypes.c_double, ctypes.POINTER(ConnectCfg),
+                _i32p, _dp, _i32p, _i32p, _i32p, ctypes.c_int64, _dp, _i64p,
+                ctypes.POINTER(ConnectSetResult)]
+            L.tcmp_plan_connect_goal_set.argtypes = [
+                vp, _dp, ctypes.c_int32, ctypes.POINTER(ConnectCfg), _i64p,
+                ctypes.POINTER(ConnectSetResult)]
         if hasattr(L, "tcmp_retime_traj"):  # absent from A/B builds of older sources
             L.tcmp_retime_traj.argtypes = [vp, _dp, _dp, _dp, _dp, ctypes.c_int64, ctypes.c_int32,
                                            ctypes.c_double, ctypes.POINTER(RetimeCfg), _dp, _dp,
@@ -813,6 +832,56 @@ class Engine:
         r = ConnectResult()
         self._check(self.L.tcmp_plan_connect(self.h, ctypes.byref(cfg), ctypes.byref(r)))
         return r
+
+    def connect_goal_set(self, nodes, cost, goals, torque_mode, payload_mass, bound=np.inf,
+                         resolutions=None, weights=None, goal_tolerance=1e-2,
+                         max_candidates=1024, passes=1):
+        """tcmp_connect_goal_set: connect_nodes with each node tried toward the nearest of
+        goals (n_goals, 7) -> connect_nodes' dict with result a ConnectSetResult, plus goal (the
+        selected ranks' goal index, -1 where not tested) and per_goal ((3, n_goals) int64: the
+        near, tested and valid counts)."""
+        self._need("tcmp_connect_goal_set")
+        q = _rows(nodes, "nodes")
+        g = np.ascontiguousarray(cost, dtype=np.float64).reshape(-1)
+        if len(g) != len(q):
+            raise ValueError("cost must hold one value per node")
+        G = _rows(goals, "goals")
+        res = None if resolutions is None else np.ascontiguousarray(resolutions, dtype=np.float64)
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
+        cfg = ConnectCfg(int(max_candidates), int(passes))
+        r = ConnectSetResult()
+        cap = min(len(q), max(int(max_candidates), 1) * max(int(passes), 1))
+        ids = np.zeros(cap, dtype=np.int32)
+        keys = np.zeros(cap)
+        gi = np.zeros(cap, dtype=np.int32)
+        ns = np.zeros(cap, dtype=np.int32)
+        nt = np.zeros(cap, dtype=np.int32)
+        node = np.zeros(8)
+        per = np.zeros((3, max(len(G), 1)), dtype=np.int64)
+        self._check(self.L.tcmp_connect_goal_set(
+            self.h, _d(q), _d(g), len(q), _d(G), len(G), float(bound), _d(res), _d(w),
+            float(goal_tolerance), int(torque_mode), float(payload_mass), ctypes.byref(cfg),
+            ids.ctypes.data_as(_i32p), _d(keys), gi.ctypes.data_as(_i32p),
+            ns.ctypes.data_as(_i32p), nt.ctypes.data_as(_i32p), cap, _d(node),
+            per.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), ctypes.byref(r)))
+        m = int(r.r.n_selected)
+        return dict(ids=ids[:m].copy(), keys=keys[:m].copy(), goal=gi[:m].copy(),
+                    nsafe=ns[:m].copy(), nsteps=nt[:m].copy(),
+                    node=node if r.r.status == CONNECT_OK else None, per_goal=per, result=r)
+
+    def plan_connect_goal_set(self, goals, max_candidates=1024, passes=1):
+        """tcmp_plan_connect_goal_set: plan_connect with each node of the open plan's tree tried
+        toward the nearest of goals (n_goals, 7); the plan's own goal is not among them unless
+        listed -> (ConnectSetResult, per_goal (3, n_goals) int64: near, tested, valid)."""
+        self._need("tcmp_plan_connect_goal_set")
+        G = _rows(goals, "goals")
+        cfg = ConnectCfg(int(max_candidates), int(passes))
+        r = ConnectSetResult()
+        per = np.zeros((3, max(len(G), 1)), dtype=np.int64)
+        self._check(self.L.tcmp_plan_connect_goal_set(
+            self.h, _d(G), len(G), ctypes.byref(cfg),
+            per.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), ctypes.byref(r)))
+        return r, per
 
     def retime(self, q, qd, qdd, mode, mass, psg=None, min_scale=1.0, max_scale=0.0):
         """tcmp_retime_traj: the largest uniform time scaling x = 1 / s^2 under which rows

@@ -23,6 +23,8 @@
 //                  k_cn_pick: validity, the new cost, the (cost, rank) minimum, the node write
 // No workgroup waits on another one anywhere: every dependence is a kernel boundary.  Device
 // memory proportional to the tree is the one 8-byte key per node.
+// The goal-set stage (tcmp_connect_set.h) shares cn_run: the key, target and pick launches come
+// from a stage object, CnSingle for the single goal.
 #pragma once
 
 namespace {
@@ -346,6 +348,31 @@ struct CnOut {
   int32_t* nsteps;
   int64_t cap;
   double* node;
+  int32_t* gidx = nullptr;  // the goal-set stage's: the ranks' goal indices
+};
+
+// What the goal-set stage (tcmp_connect_set.h) does differently hangs on cn_run's `sg`: the key
+// kernel, where the passes' targets come from, the pick kernel, and what else comes back.  This
+// is the single goal's: the launches below are the stage's own, in the order it always had.
+struct CnSingle {
+  void keys(tcmp_handle* h, unsigned grid, const PlanParams* dP, const double* rows, long long T,
+            const DevState* st, double bound, CnState* cs) {
+    hipLaunchKernelGGL(k_cn_keys, dim3(grid), dim3(256), 0, h->stream, dP, rows, T, st, bound,
+                       h->cn_key.p, cs);
+  }
+  // once, ahead of the passes: kk rows of G (m: the selected ranks)
+  int targets(tcmp_handle* h, const PlanParams* dP, size_t kk, size_t m) {
+    hipLaunchKernelGGL(k_cn_targets, dim3(grid_for((long long)kk, 256)), dim3(256), 0, h->stream,
+                       dP, (int)kk, h->cn_to.p);
+    return 0;
+  }
+  void pass_targets(tcmp_handle*, const PlanParams*, const double*, const int*, int, int) {}
+  void pick(tcmp_handle* h, const PlanParams* dP, const double* rows, const int* ids, int r0, int n,
+            const CnState* cs, DevState* st, Tree tr, long long max_nodes, CnPick* dpick) {
+    hipLaunchKernelGGL(k_cn_pick, dim3(1), dim3(1024), 0, h->stream, dP, rows, ids, h->cn_nsafe.p,
+                       h->cn_nsteps.p, h->cn_last.p, r0, n, cs, st, tr, max_nodes, dpick);
+  }
+  int finish(tcmp_handle*, size_t) { return 0; }  // copies queued ahead of the last wait
 };
 
 // The stage on T tree rows (stride 8: configuration, cost).  dP: the device copy of the goal,
@@ -353,9 +380,10 @@ struct CnOut {
 // plan's state and tree (the plan form; B and the node write are the device's), or null and an
 // empty Tree (the stand-alone form, B = bound).  The edges' launch counts into the engine's
 // scratch state.  One host wait for the counts, then one per pass.
+template <class Stage>
 int cn_run(tcmp_handle* h, const PlanParams* dP, const double* rows, long long T, DevState* st,
            Tree tr, long long max_nodes, double bound, int K, int passes, const CnOut* o,
-           tcmp_connect_result* r) {
+           tcmp_connect_result* r, Stage& sg) {
   if (int rc = h->st_sc.ensure()) return rc;
   int rc = h->cn_state.ensure(sizeof(CnState) + sizeof(CnPick));
   rc = rc ? rc : h->cn_key.ensure((size_t)T);
@@ -366,8 +394,7 @@ int cn_run(tcmp_handle* h, const PlanParams* dP, const double* rows, long long T
   const unsigned grid = (unsigned)std::min<long long>(grid_for(T, 256), (long long)h->cu_count * 8);
   HIPCHK(hipMemsetAsync(cs, 0, sizeof(CnState), h->stream));
   HIPCHK(hipMemsetAsync(&cs->key_min, 0xFF, sizeof(cs->key_min), h->stream));
-  hipLaunchKernelGGL(k_cn_keys, dim3(grid), dim3(256), 0, h->stream, dP, rows, T, st, bound,
-                     h->cn_key.p, cs);
+  sg.keys(h, grid, dP, rows, T, st, bound, cs);
   HIPCHK(hipGetLastError());
   CnState head{};  // (the fields ahead of the digits)
   const size_t head_bytes = offsetof(CnState, cnt);
@@ -383,7 +410,7 @@ int cn_run(tcmp_handle* h, const PlanParams* dP, const double* rows, long long T
   r->parent = r->rank = -1;
   r->status = TCMP_CONNECT_NONE;
   if (head.n_eligible) memcpy(&r->key_min, &head.key_min, sizeof(double));
-  if (o && (o->ids || o->keys || o->nsafe || o->nsteps) && o->cap < M)
+  if (o && (o->ids || o->keys || o->nsafe || o->nsteps || o->gidx) && o->cap < M)
     return fail(-4, "output capacity too small");
   CnPick pick{};
   if (M > 0) {
@@ -425,16 +452,14 @@ int cn_run(tcmp_handle* h, const PlanParams* dP, const double* rows, long long T
     HIPCHK(hipMemsetAsync(h->cn_nsafe.p, 0xFF, m * sizeof(int), h->stream));  // -1: not tested
     HIPCHK(hipMemsetAsync(h->cn_nsteps.p, 0xFF, m * sizeof(int), h->stream));
     HIPCHK(hipMemsetAsync(h->st_sc, 0, sizeof(DevState), h->stream));
-    hipLaunchKernelGGL(k_cn_targets, dim3(grid_for((long long)kk, 256)), dim3(256), 0, h->stream,
-                       dP, (int)kk, h->cn_to.p);
+    if ((rc = sg.targets(h, dP, kk, m))) return rc;
     for (int p = 0; p < passes && (long long)p * K < M; ++p) {
       const int r0 = p * K, n = (int)std::min<long long>(M - r0, K);
       const EdgeJob J{rows, ids + r0, h->cn_to.p, n, h->cn_nsafe.p + r0, h->cn_nsteps.p + r0,
                       h->cn_last.p, nullptr, nullptr, h->cn_rec.p};
+      sg.pass_targets(h, dP, rows, ids, r0, n);
       if ((rc = launch_edges(h, h->st_sc, J, dP))) return rc;
-      hipLaunchKernelGGL(k_cn_pick, dim3(1), dim3(1024), 0, h->stream, dP, rows, ids,
-                         h->cn_nsafe.p, h->cn_nsteps.p, h->cn_last.p, r0, n, cs, st, tr, max_nodes,
-                         dpick);
+      sg.pick(h, dP, rows, ids, r0, n, cs, st, tr, max_nodes, dpick);
       HIPCHK(hipGetLastError());
       HIPCHK(hipMemcpyAsync(&pick, dpick, sizeof(pick), hipMemcpyDeviceToHost, h->stream));
       if (int rc_s = sync_stream(h)) return rc_s;
@@ -453,6 +478,7 @@ int cn_run(tcmp_handle* h, const PlanParams* dP, const double* rows, long long T
       if (o->nsteps) rc = rc ? rc : download(h, o->nsteps, h->cn_nsteps.p, m);
       if (rc) return rc;
     }
+    if ((rc = sg.finish(h, m))) return rc;
     t.end();
     if (int rc_s = sync_stream(h)) return rc_s;
     r->edge_steps = steps;
@@ -480,25 +506,21 @@ int cn_run(tcmp_handle* h, const PlanParams* dP, const double* rows, long long T
   return 0;
 }
 
-}  // namespace
-
-extern "C" {
-
-int tcmp_connect_nodes(tcmp_handle* h, const double* nodes, const double* cost, int64_t n,
-                       const double* goal, double bound, const double* resolutions,
-                       const double* weights, double goal_tolerance, int32_t torque_mode,
-                       double payload_mass, const tcmp_connect_cfg* cfg, int32_t* ids_out,
-                       double* keys_out, int32_t* nsafe_out, int32_t* nsteps_out, int64_t cap_out,
-                       double* node_out, tcmp_connect_result* res) {
-  TCMP_ENTER(h);
+// The stand-alone forms' argument checks and staging (goal: the row that goes into P.goal): the
+// result cleared, then P and the rows of 8 filled and queued to h->dPx and h->cn_rows.  P and tmp
+// are the caller's: the copies read them until its next wait.
+int cn_stage(tcmp_handle* h, const double* nodes, const double* cost, int64_t n, const double* goal,
+             double bound, const double* resolutions, const double* weights, double goal_tolerance,
+             int32_t torque_mode, double payload_mass, int64_t cap_out, const tcmp_connect_cfg* cfg,
+             void* res, size_t res_bytes, int* K, int* passes, PlanParams& P,
+             std::vector<double>& tmp) {
   if (!nodes || !cost || !goal || !res || n < 1 || n > INT_MAX || cap_out < 0)
     return fail(-1, "bad arguments");
   if (torque_mode < 0 || torque_mode > 3) return fail(-1, "unknown torque mode");
   if (bound != bound) return fail(-1, "the bound is NaN (INFINITY: none)");
-  int K, passes;
-  if (int rc = cn_cfg(cfg, &K, &passes)) return rc;
-  memset(res, 0, sizeof(*res));
-  PlanParams P = default_params();
+  if (int rc = cn_cfg(cfg, K, passes)) return rc;
+  memset(res, 0, res_bytes);
+  P = default_params();
   for (int k = 0; k < 7; ++k) {
     if (resolutions) P.res[k] = resolutions[k];
     if (weights) P.w[k] = weights[k];
@@ -510,7 +532,7 @@ int tcmp_connect_nodes(tcmp_handle* h, const double* nodes, const double* cost, 
   P.torque_mode = torque_mode;
   P.mass = payload_mass;
   // rows of 8: the configuration, then the cost (negative costs have no ordered integer image)
-  std::vector<double> tmp((size_t)n * 8);
+  tmp.resize((size_t)n * 8);
   for (int64_t i = 0; i < n; ++i) {
     if (cost[i] < 0.0) return fail(-1, "negative node cost");
     for (int k = 0; k < 7; ++k) tmp[8 * i + k] = nodes[7 * i + k];
@@ -519,8 +541,30 @@ int tcmp_connect_nodes(tcmp_handle* h, const double* nodes, const double* cost, 
   if (int rc = h->dPx.ensure()) return rc;
   if (int rc = upload(h, h->cn_rows, tmp.data(), tmp.size())) return rc;
   HIPCHK(hipMemcpyAsync(h->dPx, &P, sizeof(P), hipMemcpyHostToDevice, h->stream));
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int tcmp_connect_nodes(tcmp_handle* h, const double* nodes, const double* cost, int64_t n,
+                       const double* goal, double bound, const double* resolutions,
+                       const double* weights, double goal_tolerance, int32_t torque_mode,
+                       double payload_mass, const tcmp_connect_cfg* cfg, int32_t* ids_out,
+                       double* keys_out, int32_t* nsafe_out, int32_t* nsteps_out, int64_t cap_out,
+                       double* node_out, tcmp_connect_result* res) {
+  TCMP_ENTER(h);
+  int K, passes;
+  PlanParams P;
+  std::vector<double> tmp;
+  if (int rc = cn_stage(h, nodes, cost, n, goal, bound, resolutions, weights, goal_tolerance,
+                        torque_mode, payload_mass, cap_out, cfg, res, sizeof(*res), &K, &passes, P,
+                        tmp))
+    return rc;
   const CnOut o{ids_out, keys_out, nsafe_out, nsteps_out, cap_out, node_out};
-  return cn_run(h, h->dPx, h->cn_rows.p, n, nullptr, Tree{}, 0, bound, K, passes, &o, res);
+  CnSingle sg;
+  return cn_run(h, h->dPx, h->cn_rows.p, n, nullptr, Tree{}, 0, bound, K, passes, &o, res, sg);
 }
 
 int tcmp_plan_connect(tcmp_handle* h, const tcmp_connect_cfg* cfg, tcmp_connect_result* res) {
@@ -534,8 +578,9 @@ int tcmp_plan_connect(tcmp_handle* h, const tcmp_connect_cfg* cfg, tcmp_connect_
   HIPCHK(hipMemcpyAsync(&T, &h->st->n_nodes, sizeof(T), hipMemcpyDeviceToHost, h->stream));
   if (int rc_s = sync_stream(h)) return rc_s;
   if (T < 1 || T > INT_MAX) return fail(-1, "no tree to connect");
+  CnSingle sg;
   if (int rc = cn_run(h, h->dP, h->cfg.p, T, h->st, Tree{h->cfg.p, h->parent.p, h->tgt.p, h->meta.p},
-                      h->P.max_nodes, INFINITY, K, passes, nullptr, res))
+                      h->P.max_nodes, INFINITY, K, passes, nullptr, res, sg))
     return rc;
   if (res->status == TCMP_CONNECT_OK) {
     // the tree has a node no round added: the host's bound on its size follows, the stored

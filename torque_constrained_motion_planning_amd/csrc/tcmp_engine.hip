@@ -1699,6 +1699,11 @@ struct tcmp_handle {
   DBuf<int> cn_nsafe, cn_nsteps;
   DBuf<unsigned char> cn_state, cn_tmp;
   long long extra_nodes = 0;
+  // goal-set connection (tcmp_connect_set.h): the goals (rows of 7), the per-goal counts (near,
+  // tested, valid: n each) with the winner's goal index behind them, the ranks' goal indices
+  DBuf<double> cset_goals;
+  DBuf<long long> cset_tab;
+  DBuf<int> cset_gidx;
   // held bodies (tcmp_set_attachments, tcmp_attach.h): the set as the kernels take it (n = 0:
   // none), its hull rows on the device, and a generation number every call bumps (round-graph key)
   AttSet att{};
@@ -4653,6 +4658,7 @@ int tcmp_plan_debug_round(tcmp_handle* h, int64_t cap, double* cand, int32_t* nn
 #include "tcmp_stage.h"
 #include "tcmp_shortcut.h"
 #include "tcmp_connect.h"
+#include "tcmp_connect_set.h"
 #include "tcmp_retime.h"
 #include "tcmp_repair.h"
 #include "tcmp_retime_runs.h"

@@ -310,3 +310,26 @@ def goal_search_for_pose(problem, start_conf, pose, torque_test, n_free=256, eng
     if stats[0].n_out < 1:
         return None, stats[0]
     return tuple(float(v) for v in q[0, 0]), stats[0]
+
+
+def goal_set_for_pose(problem, start_conf, pose, torque_test, n_goals, n_free=256, engine=None):
+    """goal_search_for_pose's search, keeping the up-to-n_goals feasible candidates nearest to
+    start_conf instead of the nearest one: the goal set of rrt_star_force_aware(goal_set=...) and
+    Engine.plan_connect_goal_set.  One Engine.goal_search(max_out=n_goals) call.  Returns
+    (list of conf tuples, nearest first, possibly empty; GoalStats)."""
+    from ._lib import engine as get_engine
+    from .scene import mesh_pack, obstacle_array
+
+    n_goals = int(n_goals)
+    if n_goals < 1:
+        raise ValueError("n_goals must be at least 1")
+    eng = get_engine() if engine is None else engine
+    eng.set_scene(obstacle_array(problem.fixed), mesh_pack(problem.fixed))
+    grasp = get_top_grasp(problem.payload)
+    gripper_pose = multiply(from_matrix(to_matrix(pose)), invert(grasp.value))
+    base_from_ee = get_base_from_ee(gripper_pose)
+    current = np.asarray(start_conf, dtype=np.float64)
+    q, _, _, _, stats = eng.goal_search(base_from_ee[None], free_grid(current[6], n_free), current,
+                                        torque_test.mode, torque_test.resolved_mass(None),
+                                        max_out=n_goals)
+    return [tuple(float(v) for v in row) for row in q[0, :stats[0].n_out]], stats[0]

@@ -179,13 +179,20 @@ def planner_fn_force_aware(start_conf, pose, problem):
     from .scene import mesh_pack, obstacle_array
     eng = get_engine()
     gs = getattr(problem, "goal_search", False)
+    others = None
     if gs:
         # opt-in: the nearest candidate that passes limits, torque test and scene, or None when
         # the grid holds none; the reference's own checks below then pass by construction
-        from .ik import goal_search_for_pose
+        from .ik import goal_search_for_pose, goal_set_for_pose
         kw = {} if gs is True else {"n_free": int(gs)}
-        grasp_conf, _ = goal_search_for_pose(problem, start_conf, pose, torque_test, engine=eng,
-                                             **kw)
+        if getattr(problem, "goal_set", 0) > 1:
+            # the N nearest: the plan aims at the first, the rest are the stage's other goals
+            confs, _ = goal_set_for_pose(problem, start_conf, pose, torque_test, problem.goal_set,
+                                         engine=eng, **kw)
+            grasp_conf, others = (confs[0], confs[1:]) if confs else (None, None)
+        else:
+            grasp_conf, _ = goal_search_for_pose(problem, start_conf, pose, torque_test,
+                                                 engine=eng, **kw)
     else:
         grasp_conf = grasp_conf_for_pose(problem, start_conf, pose, engine=eng)
     # any(pairwise_collision(robot, b) for b in obstacles) (:260): body level, link0 included
@@ -202,6 +209,7 @@ def planner_fn_force_aware(start_conf, pose, problem):
         robot, arm_joints, grasp_conf, torque_test, dynam_fn, attachments=[],
         obstacles=obstacles, self_collisions=SELF_COLLISIONS, max_time=50, custom_limits={},
         radius=resolutions / 2, max_iterations=50, start_conf=start_conf,
+        **({"goal_set": others} if others else {}),
         **({"retime": problem.retime} if getattr(problem, "retime", False) else {}),
         **({"repair": True} if getattr(problem, "repair", False) else {}))
     approach_path, approach_vels, approach_accels, approach_dts = res  # 3-tuple -> ValueError (sic)

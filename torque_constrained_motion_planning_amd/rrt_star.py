@@ -51,7 +51,7 @@ def _radius_value(radius):
 
 def rrt_star_force_aware(start, goal, distance, sample, extend, collision, torque_fn, dynam_fn,
                          radius, max_time=INF, max_iterations=INF, goal_probability=.2,
-                         *positional, connect=False, retime=False, repair=False,
+                         *positional, goal_set=None, connect=False, retime=False, repair=False,
                          informed=False, shortcut=False):
     """rrt_star.py:151-211 -> (path, vels, accels, psg) or (None, None, None, None).
     The positional order is the reference's, then shortcut: a 13th positional argument is
@@ -81,7 +81,11 @@ def rrt_star_force_aware(start, goal, distance, sample, extend, collision, torqu
     dynamics fn only.
     connect (no reference counterpart, off by default, keyword-only): after the last iteration
     the goal is tried from the best nodes of the whole tree (Engine.plan_connect), which can find
-    a goal the loop missed or a cheaper parent for it; before the shortcut.  Engine loop only."""
+    a goal the loop missed or a cheaper parent for it; before the shortcut.  Engine loop only.
+    goal_set (no reference counterpart, None by default, keyword-only): further goal
+    configurations, e.g. the other IK images of the grasp pose (ik.goal_set_for_pose).  In
+    connect's place, each node of the tree is tried toward the nearest of [goal] + goal_set
+    (Engine.plan_connect_goal_set), so the path may end at any of them.  Engine loop only."""
     if positional:
         if len(positional) > 2:
             raise TypeError("rrt_star_force_aware() takes at most 14 positional arguments "
@@ -109,7 +113,7 @@ def rrt_star_force_aware(start, goal, distance, sample, extend, collision, torqu
     if k["distance"] and k["extend"] and k["collision"] and k["torque"]:
         res, _, _ = _rrt_engine(start, goal, distance, sample, extend, collision, torque_fn,
                                 dynam_fn, radius, max_iterations, goal_probability, k["dynam"],
-                                informed, shortcut, retime, repair, connect)
+                                informed, shortcut, retime, repair, connect, goal_set)
         return res
     if repair:
         raise NotImplementedError(
@@ -118,6 +122,10 @@ def rrt_star_force_aware(start, goal, distance, sample, extend, collision, torqu
     if connect:
         raise NotImplementedError(
             "connect=True needs the package's own distance, extend, collision and torque "
+            "callbacks (the candidates are ranked and checked on the device)")
+    if goal_set is not None:
+        raise NotImplementedError(
+            "goal_set needs the package's own distance, extend, collision and torque "
             "callbacks (the candidates are ranked and checked on the device)")
     if shortcut:
         raise NotImplementedError(
@@ -250,10 +258,16 @@ def _finish(eng, dynam_fn=None, torque_fn=None, retime=None, repair=None):
     return (path, vels, accels, psg), r, out
 
 
+def _goal_list(goal, goal_set):
+    """[goal] + list(goal_set) as rows of 7: index 0 is the plan's own goal."""
+    rest = np.asarray(goal_set, dtype=np.float64).reshape(-1, 7)
+    return np.concatenate([np.asarray(goal, dtype=np.float64)[:7].reshape(1, 7), rest])
+
+
 # ---- engine loop ---------------------------------------------------------------------------
 def _rrt_engine(start, goal, distance, sample, extend, collision, torque_fn, dynam_fn, radius,
                 max_iterations, goal_probability, native_dynam=True, informed=False,
-                shortcut=False, retime=False, repair=False, connect=False):
+                shortcut=False, retime=False, repair=False, connect=False, goal_set=None):
     if max_iterations == INF:
         raise ValueError("max_iterations must be finite (the reference's time guard never "
                          "fires, rrt_star.py:159, so INF iterations never return)")
@@ -263,7 +277,8 @@ def _rrt_engine(start, goal, distance, sample, extend, collision, torque_fn, dyn
     goal = tuple(float(x) for x in goal)
     st = eng.plan_begin(start, goal, torque_fn.mode, torque_fn.payload_mass,
                         dynam_fn.execution_time if native_dynam else 0.0,
-                        max_nodes=max_iterations + 1 + bool(connect), max_batch=1,
+                        max_nodes=max_iterations + 1 + bool(connect or goal_set is not None),
+                        max_batch=1,
                         weights=distance.weights, resolutions=extend.resolutions,
                         radius=_radius_value(radius), goal_probability=goal_probability)
     if st == _lib.PLAN_START_GOAL_COLLISION:
@@ -286,7 +301,9 @@ def _rrt_engine(start, goal, distance, sample, extend, collision, torque_fn, dyn
         if found and not goal_found and informed:
             goal_cost = eng.plan_goal()[1]
         goal_found = found
-    if connect:
+    if goal_set is not None:
+        eng.plan_connect_goal_set(_goal_list(goal, goal_set))
+    elif connect:
         eng.plan_connect()
     if shortcut:
         eng.plan_shortcut()
@@ -299,7 +316,7 @@ def rrt_star_batched(start, goal, obstacles, torque_mode, payload_mass, executio
                      radius=0.01, goal_probability=0.2, device=0, engine=None,
                      self_collisions=False, shortcut=False, shortcut_passes=1, retime=False,
                      retime_max_scale=0.0, *, repair=False, connect=False,
-                     connect_candidates=1024, connect_passes=1):
+                     connect_candidates=1024, connect_passes=1, goal_set=None):
     """Engine-native batched frontier: n_samples Philox-drawn candidates, `batch` per round
     (self_collisions: the arm's self-collision pairs too, utils.py:3138-3149).
     shortcut: force-aware shortcutting of the path (Engine.plan_shortcut, shortcut_passes
@@ -317,6 +334,11 @@ def rrt_star_batched(start, goal, obstacles, torque_mode, payload_mass, executio
     connect: after the rounds and before the shortcut, the goal is tried from the best
     connect_candidates * connect_passes nodes of the whole tree (Engine.plan_connect); the tree
     is allocated one node larger for it, and raw["connect"] is the ConnectResult.
+    goal_set: further goal configurations (m, 7).  The stage runs in connect's place with each
+    node tried toward the nearest of [goal] + list(goal_set), index 0 being the plan's goal
+    (Engine.plan_connect_goal_set; connect_candidates and connect_passes apply);
+    raw["connect"] is the ConnectSetResult and raw["connect_per_goal"] the (3, 1 + m) table of
+    near, tested and valid counts.
 
     Returns ((path, vels, accels, psg) | (None,)*4, PlanResult, raw arrays)."""
     from .scene import mesh_pack, obstacle_array
@@ -325,19 +347,27 @@ def rrt_star_batched(start, goal, obstacles, torque_mode, payload_mass, executio
     eng.set_scene(obstacle_array(obstacles), mesh_pack(obstacles))
     eng.set_self_collision(self_collisions)
     st = eng.plan_begin(start, goal, torque_mode, payload_mass, execution_time,
-                        max_nodes=int(n_samples) + 1 + bool(connect), max_batch=int(batch),
+                        max_nodes=int(n_samples) + 1 + bool(connect or goal_set is not None),
+                        max_batch=int(batch),
                         seed=seed, weights=weights, resolutions=resolutions, radius=radius,
                         goal_probability=goal_probability)
     if st == _lib.PLAN_START_GOAL_COLLISION:
         return (None, None, None, None), None, None
     eng.plan_run(int(n_samples), int(batch))
-    cn = eng.plan_connect(connect_candidates, connect_passes) if connect else None
+    per = None
+    if goal_set is not None:
+        cn, per = eng.plan_connect_goal_set(_goal_list(goal, goal_set), connect_candidates,
+                                            connect_passes)
+    else:
+        cn = eng.plan_connect(connect_candidates, connect_passes) if connect else None
     sc = eng.plan_shortcut(passes=shortcut_passes) if shortcut else None
     res, r, raw = _finish(eng, retime=rt, repair={} if repair else None)
-    if shortcut or retime or connect:
+    if shortcut or retime or cn is not None:
         raw = dict(raw) if raw is not None else {}
-        if connect:
+        if cn is not None:
             raw["connect"] = cn
+        if per is not None:
+            raw["connect_per_goal"] = per
         if shortcut:
             raw["shortcut"] = sc
         if retime:

@@ -43,10 +43,17 @@ class Problem:
     and puts colliding segments back on their chords (rrt_star_force_aware(repair=True)).
     goal_search (no reference counterpart): planner_fn_force_aware picks the goal configuration
     by ik.goal_search_for_pose (every IK candidate through limits, torque test and scene, the
-    nearest feasible one) instead of the reference's random draw; an int gives n_free."""
+    nearest feasible one) instead of the reference's random draw; an int gives n_free.
+    goal_set (no reference counterpart; needs goal_search): with N > 1 the search keeps its N
+    nearest feasible candidates (ik.goal_set_for_pose); the plan aims at the nearest, and after the
+    loop every node of the tree is tried toward the nearest of all N
+    (rrt_star_force_aware(goal_set=...)).  0: off."""
 
     def __init__(self, robot, fixed, payload, payload_mass, execution_time, torque_test="arne",
-                 *, goal_search=False, repair=False, retime=False):
+                 *, goal_search=False, goal_set=0, repair=False, retime=False):
+        if goal_set and not goal_search:
+            raise ValueError("goal_set needs goal_search (the set is the search's output)")
+        self.goal_set = int(goal_set)
         self.robot = robot
         self.fixed = fixed
         self.payload = payload
